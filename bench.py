@@ -8,9 +8,14 @@ the RCCL all-gather of decoded images.  Inputs (context) are resident in HBM whe
     python bench.py --gpus 1 --steps 2 --warmup 1
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (see the driver contract): value is whole-job images/s; "roofline" is measured
-live with HIP events on the launch stream around every op of one denoiser forward; "cpu_baseline" times the
-oracle (CPU restatement of the reference) on this host's cores on a bounded sample.
+Prints ONE JSON line on rank 0 (see the driver contract): value is whole-job images/s, ms_per_step the time of one
+timed step.  A plain run sets up, warms up, times the steps and prints the line; --dump-outputs DIR also writes
+what the last timed step returned (DIR/images.npy, float32).  --full adds everything else the line can carry: the
+loop-only pass, "roofline" (measured live with HIP events on the launch stream around every op of one denoiser
+forward), the bf16 throughput mode, BASELINE configs 3 / 5 (N = 1) or 4 (N > 1), and "cpu_baseline" (the oracle,
+the CPU restatement of the reference, timed on this host's cores on a bounded sample).
+
+    python bench.py --gpus 1 --steps 2 --warmup 1 --full
 """
 import argparse
 import json
@@ -41,8 +46,16 @@ def build_model(precision, device):
     cfg["unet_config"]["params"]["precision"] = precision
     cfg["first_stage_config"]["params"]["precision"] = precision
     m = instantiate_from_config(dict(target="frido.models.diffusion.frido.FridoDiffusion", params=cfg))
-    synth.fill_module(m.model, "model.")
-    synth.fill_module(m.first_stage_model, "first_stage_model.")
+    # synth.fill_module's weights, generated on 8 threads: every tensor has its own generator (keyed by its name) and numpy releases the
+    # GIL while it draws, so the bits are the same; on one core the draw was over half of a plain run's set-up
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(8) as pool, torch.no_grad():
+        for module, prefix in ((m.model, "model."), (m.first_stage_model, "first_stage_model.")):
+            params = list(module.named_parameters())
+            for (name, p), a in zip(params, pool.map(lambda np_, pre=prefix: synth.fill_tensor(pre + np_[0], np_[1].shape), params)):
+                p.copy_(torch.from_numpy(a))
+            if hasattr(module, "invalidate"):
+                module.invalidate()
     return m.to(device).eval()
 
 
@@ -163,6 +176,37 @@ def gemm_roofline(eng, stream_ptr, precision):
                                     frac=round(v[1] / (v[0] * 1e-3) / 1e12 / peak, 4), share_of_forward=round(v[0] / total, 4))
                             for k, v in per_kernel.items() if v[2]},
                 gemm_share_of_forward=round(t_gemm / total, 4), forward_ms=round(total, 3))
+
+
+def live_roofline(model, dt_loop, args):
+    """--full: the GEMM family of one denoiser forward against the dense-f16 MFMA roof -- per-op HIP events of an eager forward of
+    every stage, the replayed forward from the loop-only pass (dt_loop) and the committed kernel trace (roofline.trace)."""
+    rt = model.model.diffusion_model.runtime()
+    eng = next(iter(rt._sampler_engines.values()))
+    roof = gemm_roofline(eng, torch.cuda.current_stream().cuda_stream, args.precision)
+    # `achieved` / `frac` come from per-op HIP events of an EAGER forward (every op bracketed by events: small kernels and
+    # cold starts are over-stated).  The same forward inside the replayed graph is faster; scaling the event times by
+    # (replayed forward time / sum of the event times) gives the in-graph figure -- an estimate, reported next to the
+    # directly measured one, never instead of it.  Cross-check: profiles/r02_gap_analysis.json (kernel trace of the sampling pass).
+    fwd_graph_ms = 1e3 * dt_loop / (len(eng.stages) * args.ddim_steps)
+    sp = torch.cuda.current_stream().cuda_stream
+    ev_ms = []
+    for stg in eng.stages:                       # event-timed forward of EVERY stage (the loop replays each S times)
+        eng.step.zero_()
+        stg.step.run(sp)
+        ev_ms.append(float(sum(stg.step.run_timed(sp))))
+    gfl = family_gflop_per_forward(eng)
+    roof["alg_gflop_per_forward_by_stage"] = [round(g, 2) for g in gfl]
+    # `forward_ms` of this block = the forward as the sampler RUNS it (loop-only pass / forwards: graph replays); the per-op event sum it
+    # used to hold is `forward_ms_events` (eager, every op bracketed by events: longer) -- forward_ms x forwards <= ms_per_step holds
+    roof["forward_ms_events"] = roof["forward_ms"]
+    roof["forward_ms"] = round(fwd_graph_ms, 3)
+    roof["trace"] = trace_roofline(gfl, roof["peak"])
+    if ev_ms and fwd_graph_ms > 0:
+        # ratio only: small launches carry most of the event overhead, so scaling the GEMM figure by it would flatter it
+        roof["event_vs_graph"] = {"forward_ms_replayed": round(fwd_graph_ms, 3), "forward_ms_events": [round(t, 3) for t in ev_ms],
+                                  "event_to_graph_ratio": round((sum(ev_ms) / len(ev_ms)) / fwd_graph_ms, 3)}
+    return roof
 
 
 def _cpu_model():
@@ -320,9 +364,28 @@ def config4_record(total, per_gpu, world, seconds, ddim_steps, stub=False):
     return rec
 
 
+DUMP_BYTES = 64 << 20      # --dump-outputs budget over all arrays
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` (name -> tensor) as <path>/<name>.npy in float32.  An array larger than the budget keeps a
+    fixed, seeded sample of its leading (batch) index, sorted, so two runs of the same command write the same images."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.nbytes > budget:
+            keep = max(1, budget // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def relaunch(n):
-    """Re-exec this command line under torch.distributed.run with one rank per GPU (rendezvous on 127.0.0.1, a free port)."""
+    """Run this command line under torch.distributed.run with one rank per GPU (rendezvous on 127.0.0.1, a free port) as a child
+    process and exit with its status."""
     import socket
+    import subprocess
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
@@ -331,7 +394,7 @@ def relaunch(n):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))
 
 
 def stub_main(args, dist, use_dist, world, rank):
@@ -365,8 +428,10 @@ def stub_main(args, dist, use_dist, world, rank):
         dist.all_gather(allt, torch.tensor([dt], dtype=torch.float64))
         per_rank = [float(t.item()) for t in allt]
         dt = max(per_rank)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"images": img})
     cfg4 = None
-    if world > 1 and B == 16 and not args.no_config4:        # the config-4 pass of the real N > 1 job (32 per GPU), same collective
+    if args.full and world > 1 and B == 16 and not args.no_config4:        # the config-4 pass of the real N > 1 job (32 per GPU), same collective
         tot4 = 32 * world
         lo4, hi4 = shard_range(tot4, rank, world)
         if use_dist:
@@ -405,12 +470,19 @@ def main():
     ap.add_argument("--image-dtype", default="uint8", choices=["uint8", "float32"],
                     help="what a step hands back (and, N > 1, all-gathers): the uint8 HWC images of scripts/sample_diffusion.py "
                          "custom_to_np, written by the decoder's last epilogue (default), or decode_first_stage's f32 NCHW tensor")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also run what it does not need: the loop-only pass, the per-op roofline, the bf16 "
+                         "throughput mode, configs 3 / 5 (N = 1), the config-4 pass (N > 1) and the CPU baseline; the --no-* options "
+                         "below switch single legs of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (the images) as DIR/<name>.npy in float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the short passes of BASELINE configs 3 (t2i f16f8, B = 32, PLMS-100 + CFG 1.5) and 5 (512^2, 3 scales, B = 8) "
                          "that the N = 1 line carries in `extra.other_configs`")
     ap.add_argument("--no-config4", action="store_true",
-                    help="N > 1 only: skip the extra pass at 32 images per GPU (BASELINE config 4's shard) reported in extra.config4_B32_per_gpu")
+                    help="N > 1 with --full: skip the extra pass at 32 images per GPU (BASELINE config 4's shard) reported in "
+                         "extra.config4_B32_per_gpu")
     ap.add_argument("--no-bf16-extra", "--no-parity-mode", dest="no_bf16_extra", action="store_true",
                     help="skip the extra bf16 (throughput-mode) pass at N = 1")
     ap.add_argument("--cpu-threads", type=int, default=0)
@@ -504,25 +576,28 @@ def main():
         dt = max(per_rank)                      # the slowest rank sets the job's time
     assert img.shape == ((total, 256, 256, 3) if args.image_dtype == "uint8" else (total, 3, 256, 256))
     assert args.image_dtype == "uint8" or bool(torch.isfinite(img).all()) or debug_env
-    # the reference's own throughput definition (scripts/sample_diffusion.py:188-204): the sampling loop only, no decode
-    from frido_amd.samplers import DDIMSampler
-    unet = model.model.diffusion_model
-    fence()
-    t0 = time.perf_counter()
-    z_chk, _ = DDIMSampler(model).sample(S=args.ddim_steps, batch_size=B, shape=(unet.in_channels, unet.image_size, unet.image_size),
-                                         conditioning=ctx, num_stage=unet.num_stage, eta=1.0, verbose=False, noise="philox", seed=999,
-                                         sample0=lo, log_every_t=10 ** 9)
-    fence()
-    dt_loop = time.perf_counter() - t0
-    assert (bool(torch.isfinite(z_chk).all()) and float(z_chk.std()) > 0.05 and int(img.max()) > int(img.min())) or debug_env, "degenerate samples"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"images": img})
+    if args.full:
+        # the reference's own throughput definition (scripts/sample_diffusion.py:188-204): the sampling loop only, no decode
+        from frido_amd.samplers import DDIMSampler
+        unet = model.model.diffusion_model
+        fence()
+        t0 = time.perf_counter()
+        z_chk, _ = DDIMSampler(model).sample(S=args.ddim_steps, batch_size=B, shape=(unet.in_channels, unet.image_size, unet.image_size),
+                                             conditioning=ctx, num_stage=unet.num_stage, eta=1.0, verbose=False, noise="philox", seed=999,
+                                             sample0=lo, log_every_t=10 ** 9)
+        fence()
+        dt_loop = time.perf_counter() - t0
+        assert (bool(torch.isfinite(z_chk).all()) and float(z_chk.std()) > 0.05 and int(img.max()) > int(img.min())) or debug_env, "degenerate samples"
 
     status_after_timed = _lib.status_flags()          # every pass above ran with check_status=False: this is the word of ALL of them
 
     # (r06, r05 verdict next 8) BASELINE config 4 is "batch 256 sharded over 8 GPUs" = 32 per GPU; the driver's scaling spelling
     # (--gpus N, default batch 16) would never run it, so every N > 1 job adds ONE warm + ONE timed pass at 32 per GPU (same model,
-    # same collective) and reports it in `extra.config4_B32_per_gpu`.  --no-config4 skips it; N = 1 has it as tools' --batch 32 line.
+    # same collective) and reports it in `extra.config4_B32_per_gpu` (--full).  --no-config4 skips it; N = 1 has it as tools' --batch 32 line.
     cfg4 = None
-    if world > 1 and B == 16 and not args.no_config4:
+    if args.full and world > 1 and B == 16 and not args.no_config4:
         B4 = 32
         tot4 = B4 * world
         lo4, hi4 = shard_range(tot4, rank, world)
@@ -544,31 +619,6 @@ def main():
         del img4, ctx4
 
     if rank == 0:
-        rt = model.model.diffusion_model.runtime()
-        eng = next(iter(rt._sampler_engines.values()))
-        roof = gemm_roofline(eng, torch.cuda.current_stream().cuda_stream, args.precision)
-        # `achieved` / `frac` come from per-op HIP events of an EAGER forward (every op bracketed by events: small kernels and
-        # cold starts are over-stated).  The same forward inside the replayed graph is faster; scaling the event times by
-        # (replayed forward time / sum of the event times) gives the in-graph figure -- an estimate, reported next to the
-        # directly measured one, never instead of it.  Cross-check: profiles/r02_gap_analysis.json (kernel trace of the sampling pass).
-        fwd_graph_ms = 1e3 * dt_loop / (len(eng.stages) * args.ddim_steps)
-        sp = torch.cuda.current_stream().cuda_stream
-        ev_ms = []
-        for stg in eng.stages:                       # event-timed forward of EVERY stage (the loop replays each S times)
-            eng.step.zero_()
-            stg.step.run(sp)
-            ev_ms.append(float(sum(stg.step.run_timed(sp))))
-        gfl = family_gflop_per_forward(eng)
-        roof["alg_gflop_per_forward_by_stage"] = [round(g, 2) for g in gfl]
-        # `forward_ms` of this block = the forward as the sampler RUNS it (loop-only pass / forwards: graph replays); the per-op event sum it
-        # used to hold is `forward_ms_events` (eager, every op bracketed by events: longer) -- forward_ms x forwards <= ms_per_step holds
-        roof["forward_ms_events"] = roof["forward_ms"]
-        roof["forward_ms"] = round(fwd_graph_ms, 3)
-        roof["trace"] = trace_roofline(gfl, roof["peak"])
-        if ev_ms and fwd_graph_ms > 0:
-            # ratio only: small launches carry most of the event overhead, so scaling the GEMM figure by it would flatter it
-            roof["event_vs_graph"] = {"forward_ms_replayed": round(fwd_graph_ms, 3), "forward_ms_events": [round(t, 3) for t in ev_ms],
-                                      "event_to_graph_ratio": round((sum(ev_ms) / len(ev_ms)) / fwd_graph_ms, 3)}
         out = {
             "metric": f"images/sec @ DDIM-{args.ddim_steps}, COCO layout2img 256x256", "value": round(total * args.steps / dt, 4),
             "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -585,21 +635,22 @@ def main():
                                    + ("; extra.config4_B32_per_gpu: the same job at 32 per GPU (BASELINE config 4's shard), one timed pass" if cfg4 else ""),
                        "global_batch": total, "denoiser_forwards_per_step": 2 * args.ddim_steps, "parallelism": f"dp{world}",
                        "env": {k: v for k, v in sorted(os.environ.items()) if k.startswith("FRIDO_") and k != "FRIDO_TUNE_CACHE"}},
-            "roofline": roof,
             # whole job against the same roof: SURVEY 8(d)'s canonical (deduplicated) algorithmic FLOPs per image of this workload
             # -- S x (208.72 + 208.76) GFLOP of denoiser forwards + 129.6 one-time (SPADE maps, cross K/V, emb) + 799.7 decode
             "whole_step": whole_step(args.ddim_steps, total * args.steps / dt, world),
-            "loop_only_value": round(total / dt_loop, 4),         # sample_diffusion.py's `throughput`: sampler loop without decode
             "per_rank_ms_per_step": [round(1e3 * t / args.steps, 2) for t in per_rank],
-            # sticky numerics word of the library, read ONCE after the warm-up, timed and loop-only passes, none of which cleared it
+            # sticky numerics word of the library, read ONCE after the warm-up, timed and (--full) loop-only passes, none of which cleared it
             # (frido_status_flags): 0 = no fp16 operand plane saturated, no normalisation statistic was NaN / inf anywhere in that work
             "status_flags": status_after_timed,
         }
+        if args.full:
+            out["roofline"] = live_roofline(model, dt_loop, args)
+            out["loop_only_value"] = round(total / dt_loop, 4)        # sample_diffusion.py's `throughput`: sampler loop without decode
         if debug_env:
             out["debug_work_skipped"] = True
         if cfg4:
             out.setdefault("extra", {})["config4_B32_per_gpu"] = cfg4
-        if world == 1 and args.precision == "bf16x3" and not args.no_bf16_extra:
+        if args.full and world == 1 and args.precision == "bf16x3" and not args.no_bf16_extra:
             # the same workload in plain bf16 (one plane, one MFMA pass): a THROUGHPUT mode that fails the north star's <= 1e-3
             # tolerance (its measured error is in the committed E2E record) -- reported for reference, never as `value`
             del model
@@ -622,7 +673,7 @@ def main():
                     break
             out["extra"] = {"bf16_throughput_mode": extra}
             del m1
-        if world == 1 and args.precision == "bf16x3" and not args.no_other_configs and args.batch == 16 and args.ddim_steps == 200:
+        if args.full and world == 1 and args.precision == "bf16x3" and not args.no_other_configs and args.batch == 16 and args.ddim_steps == 200:
             # (r05, r04 verdict weak 11) the other single-GPU workloads of BASELINE.json, timed by THIS command so that the driver's
             # record holds them: config 3 (t2i f16f8, batch 32, PLMS-100 + CFG 1.5) and config 5's per-GPU shard (512 x 512, three
             # scales, batch 8, DDIM-200) -- short passes (1 warm + 2 / 1 timed), same arithmetic as `value`; not the headline metric
@@ -646,7 +697,7 @@ def main():
             out.setdefault("extra", {})["other_configs"] = others
             # (r06) the two values again as a flat top-level dict: a record that keeps only the first level of the line still holds them
             out["other_configs_images_per_s"] = {k: v.get("value", v.get("error")) for k, v in others.items()}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # B in {1, 4} x {8, 16, 32, all physical cores} torch threads; `cores` = the best point's thread count
             try:      # (r05, advisor) a failure of the CPU leg must not lose the GPU measurement above
                 out["cpu_baseline"] = cpu_baseline(args.cpu_threads, full_ddim50=not args.no_cpu_ddim50)

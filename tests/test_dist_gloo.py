@@ -114,7 +114,7 @@ def _bench_line(args, env_extra, timeout=300):
 
 
 def test_bench_gpus_n_self_launches_one_rank_per_gpu():
-    """`python bench.py --gpus 2 ...` typed WITHOUT torch.distributed.run (the driver's N = 1 spelling with a larger N) re-execs
+    """`python bench.py --gpus 2 ...` typed WITHOUT torch.distributed.run (the driver's N = 1 spelling with a larger N) starts
     itself as a 2-rank job and prints one whole-job JSON line; FRIDO_BENCH_STUB swaps the HIP sampler for a CPU function of the
     global sample index so the launcher, shard arithmetic, barrier-bracketed timing and max-over-ranks run here over gloo."""
     line = _bench_line(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "5"], {})
@@ -142,15 +142,38 @@ def test_bench_n_gt_1_line_carries_the_config4_pass():
     """(r06) BASELINE config 4 is 256 images over 8 GPUs = 32 per GPU; the driver's scaling spelling runs the default 16 per GPU, so every
     N > 1 job adds one pass at 32 per GPU and reports it as `extra.config4_B32_per_gpu` (named in config.workload).  Stub job over gloo:
     the record's arithmetic and the opt-out."""
-    line = _bench_line(["--gpus", "2", "--steps", "1", "--warmup", "0"], {})
+    line = _bench_line(["--gpus", "2", "--steps", "1", "--warmup", "0", "--full"], {})
     c4 = line["extra"]["config4_B32_per_gpu"]
     assert c4["per_gpu_batch"] == 32 and c4["global_batch"] == 64 and c4["n_gpus"] == 2 and c4["value"] > 0 and c4["unit"] == "images/s"
     assert abs(c4["value"] - 64 / (c4["ms_per_step"] * 1e-3)) / c4["value"] < 1e-2 and "config4_B32_per_gpu" in line["config"]["workload"]
     assert line["config"]["global_batch"] == 32                      # the headline workload is still 16 per GPU
-    off = _bench_line(["--gpus", "2", "--steps", "1", "--warmup", "0", "--no-config4"], {})
+    off = _bench_line(["--gpus", "2", "--steps", "1", "--warmup", "0", "--full", "--no-config4"], {})
     assert "extra" not in off
-    other = _bench_line(["--gpus", "2", "--steps", "1", "--warmup", "0", "--batch", "5"], {})       # not the default batch: not config 4's job
+    other = _bench_line(["--gpus", "2", "--steps", "1", "--warmup", "0", "--full", "--batch", "5"], {})       # not the default batch: not config 4's job
     assert "extra" not in other
+    plain = _bench_line(["--gpus", "2", "--steps", "1", "--warmup", "0"], {})          # a plain run: the headline job only
+    assert "extra" not in plain and "config4_B32_per_gpu" not in plain["config"]["workload"]
+
+
+def test_bench_steps_and_dump_outputs(tmp_path):
+    """--steps sets the number of timed steps, ms_per_step is one of them, and --dump-outputs DIR writes what the last timed step
+    returned as float32 .npy: the same arrays from two runs of the same command (stub job: a step returns a function of the step
+    index and the global sample index), at N = 1 and from rank 0 of a two-rank job."""
+    import numpy as np
+    runs = []
+    for tag, gpus in (("a", "1"), ("b", "1"), ("c", "2")):
+        d = tmp_path / tag
+        line = _bench_line(["--gpus", gpus, "--steps", "3", "--warmup", "2", "--batch", "4", "--dump-outputs", str(d)], {})
+        assert line["steps"] == 3 and line["warmup"] == 2 and line["ms_per_step"] >= 10.0      # the stub step sleeps 10 ms
+        assert abs(line["value"] - line["config"]["global_batch"] * 3 / (line["ms_per_step"] * 3e-3)) / line["value"] < 1e-3
+        assert sorted(p.name for p in d.iterdir()) == ["images.npy"]
+        runs.append(np.load(d / "images.npy"))
+    total = 4
+    for img in runs[:2]:
+        assert img.dtype == np.float32 and img.shape == (total, 3, 8, 8)
+        assert np.array_equal(img[:, 0, 0, 0], 1000.0 * 4 + np.arange(total, dtype=np.float32))      # the last timed step (k = 2 + 3 - 1)
+    assert np.array_equal(runs[0], runs[1])
+    assert runs[2].shape == (2 * total, 3, 8, 8) and np.array_equal(runs[2][:, 0, 0, 0], 4000.0 + np.arange(2 * total, dtype=np.float32))
 
 
 def test_bench_refuses_cleanly_when_the_node_has_fewer_devices_than_ranks():

@@ -901,13 +901,33 @@ def test_bench_under_torchrun_takes_the_rccl_path_at_n1():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr",
                           "127.0.0.1", "--master-port", "29533", os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "1",
-                          "--warmup", "0", "--batch", "2", "--ddim-steps", "4", "--no-cpu-baseline", "--no-bf16-extra"],
+                          "--warmup", "0", "--batch", "2", "--ddim-steps", "4", "--full", "--no-cpu-baseline", "--no-bf16-extra"],
                          capture_output=True, text=True, env=env, timeout=900, cwd=repo)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["scaling"] == "weak" and len(d["per_rank_ms_per_step"]) == 1
     assert d["config"]["global_batch"] == 2 and "roofline" in d
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """`bench.py` without --full: the warm-up, the timed steps and the line (none of the --full legs), and --dump-outputs DIR writes the
+    uint8 images the last timed step returned as DIR/images.npy in float32."""
+    import json
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
+                          "--ddim-steps", "4", "--dump-outputs", str(tmp_path / "out")],
+                         capture_output=True, text=True, timeout=900, cwd=repo)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["unit"] == "images/s"
+    assert abs(d["value"] - 2 * 2 / (d["ms_per_step"] * 2e-3)) / d["value"] < 1e-2 and d["dtype"].startswith("f16x3")
+    assert not {"roofline", "loop_only_value", "extra", "cpu_baseline", "other_configs_images_per_s"} & set(d)
+    img = np.load(tmp_path / "out" / "images.npy")
+    assert img.dtype == np.float32 and img.shape == (2, 256, 256, 3)
+    assert np.array_equal(img, np.round(img)) and img.min() >= 0 and img.max() <= 255 and img.max() > img.min()
 
 
 def test_vq_full_width_encode_matches_reference_golden():

@@ -12,7 +12,7 @@
 # r05_gn_fused_v4_ab: `tools/ab.sh env FRIDO_GN_FUSED_V4 1 0`; r04_x3_side_stream_ab: `tools/ab.sh env FRIDO_SIDE_STREAM 0 1`.
 MODE=${1:?env | tuned | lib | libtuned}; shift
 ROUNDS=${ROUNDS:-2}
-B="--steps 2 --warmup 1 --no-cpu-baseline --no-bf16-extra --no-other-configs $EXTRA"
+B="--steps 2 --warmup 1 --full --no-cpu-baseline --no-bf16-extra --no-other-configs $EXTRA"
 line() { grep -v amdgpu.ids | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1', d['value'], 'images/s', d['ms_per_step'], 'ms/batch', 'fwd', d['roofline']['forward_ms'], 'gemm TF', d['roofline']['achieved'])"; }
 case $MODE in
   env|tuned)

@@ -28,12 +28,12 @@ rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum --output-
 python $R/tools/pmc_instances.py /tmp/pmc_l2 /tmp/pmc_grbm --top 45 > $OUT/${TAG}_pmc_l2_instances.json 2> $OUT/${TAG}_pmc_l2_instances.err
 fi
 # ---- kernel trace of the bench command (the headline workload only: the other configs of the default line stay out of the window) ----
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ktrace -- python $R/bench.py --precision $PREC --steps 1 --warmup 1 --no-cpu-baseline --no-bf16-extra --no-other-configs > $OUT/${TAG}_bench_under_trace.json 2> /tmp/ktrace.log
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ktrace -- python $R/bench.py --precision $PREC --steps 1 --warmup 1 --full --no-cpu-baseline --no-bf16-extra --no-other-configs > $OUT/${TAG}_bench_under_trace.json 2> /tmp/ktrace.log
 cp $(ls /tmp/ktrace/*/*kernel_stats.csv | head -1) $OUT/${TAG}_bench_kernel_stats.csv
 python $R/tools/gap_analysis.py /tmp/ktrace > $OUT/${TAG}_gap_analysis.json 2> $OUT/${TAG}_gap.err
 [ "$ONLY" = trace ] && exit 0
 # ---- clocks / power while the bench runs ----
-(python $R/bench.py --precision $PREC --steps 3 --warmup 1 --no-cpu-baseline --no-bf16-extra --no-other-configs > $OUT/${TAG}_bench_smi_run.json 2>/dev/null) &
+(python $R/bench.py --precision $PREC --steps 3 --warmup 1 --full --no-cpu-baseline --no-bf16-extra --no-other-configs > $OUT/${TAG}_bench_smi_run.json 2>/dev/null) &
 BP=$!
 : > $OUT/${TAG}_smi_log.txt
 while kill -0 $BP 2>/dev/null; do
