@@ -10,15 +10,30 @@ Restates the constructor loops of the reference:
 from dataclasses import dataclass, field
 from typing import List, Optional
 
-__all__ = ["UNetArch", "unet_arch", "DecoderArch", "decoder_arch", "EncoderArch", "encoder_arch"]
+__all__ = ["UNetArch", "unet_arch", "DecoderArch", "decoder_arch", "EncoderArch", "encoder_arch", "MH_HEAD_DIMS",
+           "check_attention_heads"]
+
+# head dimensions the multi-head flash kernel (csrc/flash_mh.hip) is instantiated for; the library answers the same through
+# frido_attn_mh_supported (tests compare the two).  Kept here so that a model is refused at construction, before any library is loaded.
+MH_HEAD_DIMS = (32, 64)
+
+
+def check_attention_heads(heads, d, where="attention"):
+    """Raise NotImplementedError for a (heads, head dim) pair no kernel serves: one head takes the single-head kernels (any d that is
+    a multiple of 32), several heads need d in MH_HEAD_DIMS."""
+    if heads > 1 and d not in MH_HEAD_DIMS:
+        raise NotImplementedError(f"{where}: {heads} heads of {d} channels -- the multi-head attention kernel is built for head "
+                                  f"dimensions {', '.join(map(str, MH_HEAD_DIMS))} only (one head: any multiple of 32)")
 
 
 @dataclass
 class Blk:
-    kind: str            # 'res' | 'st' | 'down' | 'up'
+    kind: str            # 'res' | 'st' | 'attn' | 'down' | 'up'
     prefix: str          # state_dict prefix relative to the U-Net root, e.g. 'input_blocks.3.0'
     cin: int
     cout: int
+    heads: int = 1       # 'attn' (AttentionBlock, pyunet.py:303-358): number of heads of cin / heads channels ...
+    new_order: bool = False      # ... and whether qkv is split before the heads (QKVAttention) or after (QKVAttentionLegacy)
 
 
 @dataclass
@@ -37,6 +52,12 @@ class UNetArch:
     skip_channels: List[int] = field(default_factory=list)   # channels pushed on the skip stack
     image_size: int = 64
     transformer_depth: int = 1     # BasicTransformerBlocks per SpatialTransformer (attention.py:274-277)
+    num_classes: Optional[int] = None      # class-conditional denoiser: label_emb (pyunet.py:567-571) ...
+    use_embed: bool = False                # ... nn.Embedding (y int64 [B]) or nn.Linear (y float [B, num_classes])
+
+    def attention_sites(self):
+        """Every 'st' / 'attn' block in forward order."""
+        return [blk for grp in (self.input_blocks + [self.middle] + self.output_blocks) for blk in grp if blk.kind in ("st", "attn")]
 
 
 def unet_arch(cfg) -> UNetArch:
@@ -45,17 +66,51 @@ def unet_arch(cfg) -> UNetArch:
     nres = cfg["num_res_blocks"]
     attn_res = set(cfg["attention_resolutions"])
     use_st = cfg.get("use_spatial_transformer", False)
-    if not use_st:
-        raise NotImplementedError("only the SpatialTransformer denoiser (every shipped Frido config) is built")
     if cfg.get("resblock_updown", False) or cfg.get("use_scale_shift_norm", False):
         raise NotImplementedError("resblock_updown / use_scale_shift_norm are not used by any Frido config")
     depth = int(cfg.get("transformer_depth", 1))
     if depth < 1:
         raise ValueError("transformer_depth must be >= 1")
+    if not use_st and cfg.get("context_dim") is not None:      # pyunet.py:516-517
+        raise ValueError("context_dim needs use_spatial_transformer=True: the AttentionBlock denoiser has no cross-attention")
+    if use_st and not cfg.get("legacy", True):
+        raise NotImplementedError("legacy=False with use_spatial_transformer=True (multi-head SpatialTransformer) is not built")
     a = UNetArch(model_channels=mc, time_embed_dim=4 * mc, context_dim=cfg.get("context_dim"),
                  num_stage=cfg.get("num_stage", 1), splits=list(cfg.get("split_embed_dim_list", [])),
                  use_spade=cfg.get("use_SPADE_norm", False), use_split_head=cfg.get("use_split_head", False),
-                 in_channels=cfg["in_channels"], image_size=cfg.get("image_size", 64), transformer_depth=depth)
+                 in_channels=cfg["in_channels"], image_size=cfg.get("image_size", 64), transformer_depth=depth,
+                 num_classes=cfg.get("num_classes"), use_embed=bool(cfg.get("use_embed", False)))
+    # head count of an AttentionBlock site, by the reference's rules: the constructor loops (pyunet.py:633-640, 686-693, 751-758) carry
+    # `num_heads` from site to site, legacy=True forces it to 1 and passes num_head_channels through, the output path hands
+    # num_heads_upsample to the block, and AttentionBlock.__init__ (323-329) lets a head width override the count
+    nh = [cfg.get("num_heads", -1)]
+    nhc = cfg.get("num_head_channels", -1)
+    nh_up = cfg.get("num_heads_upsample", -1)
+    nh_up = nh[0] if nh_up == -1 else nh_up
+    legacy = cfg.get("legacy", True)
+    new_order = bool(cfg.get("use_new_attention_order", False))
+
+    def attn(prefix, ch, out_path=False):
+        if use_st:
+            return Blk("st", prefix, ch, ch)
+        if nhc == -1:
+            dim_head = ch // nh[0]
+        else:
+            nh[0] = ch // nhc
+            dim_head = nhc
+        if legacy:
+            nh[0] = 1
+            dim_head = nhc
+        heads = nh_up if out_path else nh[0]
+        if dim_head != -1:
+            if dim_head <= 0 or ch % dim_head:
+                raise ValueError(f"{prefix}: q,k,v channels {ch} is not divisible by num_head_channels {dim_head}")
+            heads = ch // dim_head
+        if heads < 1 or ch % heads:
+            raise ValueError(f"{prefix}: {ch} channels do not split into {heads} heads")
+        check_attention_heads(heads, ch // heads, f"AttentionBlock {prefix} ({ch} channels)")
+        return Blk("attn", prefix, ch, ch, heads=heads, new_order=new_order)
+
     # pyunet.py:600-609: with the split head input_blocks starts empty, otherwise block 0 is the conv
     idx = 0 if a.use_split_head else 1
     chans = [mc]
@@ -66,7 +121,7 @@ def unet_arch(cfg) -> UNetArch:
             blk = [Blk("res", f"input_blocks.{idx}.0", ch, m * mc)]
             ch = m * mc
             if ds in attn_res:
-                blk.append(Blk("st", f"input_blocks.{idx}.1", ch, ch))
+                blk.append(attn(f"input_blocks.{idx}.1", ch))
             a.input_blocks.append(blk)
             chans.append(ch)
             idx += 1
@@ -76,7 +131,7 @@ def unet_arch(cfg) -> UNetArch:
             idx += 1
             ds *= 2
     a.skip_channels = list(chans)
-    a.middle = [Blk("res", "middle_block.0", ch, ch), Blk("st", "middle_block.1", ch, ch),
+    a.middle = [Blk("res", "middle_block.0", ch, ch), attn("middle_block.1", ch),
                 Blk("res", "middle_block.2", ch, ch)]
     oidx = 0
     for level, m in list(enumerate(mult))[::-1]:
@@ -86,7 +141,7 @@ def unet_arch(cfg) -> UNetArch:
             ch = mc * m
             j = 1
             if ds in attn_res:
-                blk.append(Blk("st", f"output_blocks.{oidx}.{j}", ch, ch))
+                blk.append(attn(f"output_blocks.{oidx}.{j}", ch, out_path=True))
                 j += 1
             if level and i == nres:
                 blk.append(Blk("up", f"output_blocks.{oidx}.{j}", ch, ch))

@@ -9,6 +9,7 @@ import os
 import torch
 
 from . import _lib
+from .arch import MH_HEAD_DIMS, check_attention_heads      # noqa: F401  (re-exported: the kernel-level entry points check the same set)
 from .engine import (Operand, POperand, F32, Alias, Pool, Prog, pack_matrix, pack_conv_weight, rup)
 
 ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2
@@ -665,6 +666,37 @@ class Builder:
         self.prog.gemm(Nq, d, Np, p, vT, batch=B, lda=Np, ldb=Np, a_bs=Nq * Np, b_bs=d * Np, out_op=o.ptr,
                        oo_bs=Nq * d, ldoo=d, oo_lo=o.lo)
         p.free()
+        return o
+
+    def attention_heads(self, qkv, ldqkv, vT, B, N, heads, d, *, legacy=True, **one_head):
+        """Self-attention core of the reference's AttentionBlock (pyunet.py:303-358) over N tokens per sample.  qkv: operand rows
+        [B*N] (row stride ldqkv >= 3 C, C = heads * d) as the qkv projection left them; vT: operand [B][C][N_pad] with head h at rows
+        h * d .. (zero beyond N) -- the V rows of the weight gathered head-major by the caller.  Head h reads q / k at columns
+        3 d h / 3 d h + d (legacy = True: QKVAttentionLegacy, pyunet.py:393-396) or h d / C + h d (legacy = False: QKVAttention,
+        :427-432).  Returns operand O [B*N][C] with head h at columns h * d .. (both orders' a.reshape(bs, -1, length)).
+        scale = d ** -0.5 (the reference scales q and k by d ** -0.25 each).
+        One head: Builder.attention with its keyword arguments (`one_head`: stream / residual / bias_ptr ... for a folded output
+        projection).  Several heads: the multi-head flash kernel, d in MH_HEAD_DIMS; anything else raises NotImplementedError."""
+        C = heads * d
+        check_attention_heads(heads, d)
+        if heads == 1:
+            return self.attention(qkv, ldqkv, qkv, ldqkv, vT, B, N, N, d, q_off=0, k_off=C, **one_head)
+        if one_head:
+            raise TypeError(f"attention_heads: {sorted(one_head)} apply to the one-head path only")
+        k_off, hs = (d, 3 * d) if legacy else (C, d)
+        return self.attention_mh(qkv, ldqkv, 0, hs, qkv, ldqkv, k_off, hs, vT, B, N, N, heads, d)
+
+    def attention_mh(self, q, ldq, q_off, q_hs, k, ldk, k_off, k_hs, vT, B, Nq, Nk, heads, d):
+        """The multi-head flash kernel (csrc/flash_mh.hip) on explicit addressing: head h reads q at columns q_off + h * q_hs of the
+        rows [B*Nq] of `q` (row stride ldq), k at columns k_off + h * k_hs of the rows [B][Nk] of `k`, v^T at rows h * d .. of
+        vT [B][heads * d][Nk_pad]; returns operand O [B*Nq][heads * d].  Any Nq, any Nk; d in MH_HEAD_DIMS."""
+        if not _lib.lib().frido_attn_mh_supported(d):
+            raise _lib.FridoHipError(f"libfrido_hip.so has no multi-head attention kernel for head dimension {d}")
+        C, Np = heads * d, rup(Nk, 32)
+        o = self.op(B * Nq, C)
+        self.prog.emit("FRIDO_OP_ATTN_MH", Q=q.ptr + 2 * q_off, q_lo=q.lo, ldq=ldq, q_hs=q_hs, K=k.ptr + 2 * k_off, k_lo=k.lo,
+                       k_bs=Nk * ldk, ldk=ldk, k_hs=k_hs, VT=vT.ptr, vt_lo=vT.lo, vt_bs=C * Np, ldvt=Np, out_op=o.ptr, out_lo=o.lo,
+                       ldo=C, B=B, heads=heads, Nq=Nq, Nk=Nk, d=d, nsplit=self.nsplit, alpha=float(d) ** -0.5)
         return o
 
     @staticmethod

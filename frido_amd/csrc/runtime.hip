@@ -60,6 +60,7 @@ int run_one(const FridoOp& op, frido_stream_t s) {
         case FRIDO_OP_COPY: return frido_copy(&op.u.copy, s);
         case FRIDO_OP_ATTN_FLASH: return frido_attn_flash(&op.u.attn_small, s);
         case FRIDO_OP_L2NORM: return frido_l2norm(&op.u.l2norm, s);
+        case FRIDO_OP_ATTN_MH: return frido_attn_mh(&op.u.attn_mh, s);
         default:
             frido_set_error("frido_run: unknown op kind %d", op.kind);
             return FRIDO_EINVAL;
@@ -304,6 +305,7 @@ extern "C" int frido_sizeof_desc(int32_t kind) {
         case FRIDO_OP_ATTN_FLASH: return sizeof(FridoAttnSmall);
         case FRIDO_OP_SYNC: return sizeof(FridoSync);
         case FRIDO_OP_L2NORM: return sizeof(FridoL2Norm);
+        case FRIDO_OP_ATTN_MH: return sizeof(FridoAttnMh);
         default: return -1;
     }
 }
@@ -386,7 +388,7 @@ extern "C" int frido_status_poll(frido_stream_t stream, uint32_t* flags, int32_t
     return FRIDO_OK;
 }
 
-// diagnostic: the word of ONE translation unit (registration = link order: igemm, convgn, norm, misc, attn, flash, runtime); -1 past the end
+// diagnostic: the word of ONE translation unit (registration = link order: igemm, convgn, norm, misc, attn, flash, flash_mh, runtime); -1 past the end
 extern "C" int frido_status_word_of(int32_t idx, uint32_t* word) {
     if (idx < 0 || idx >= (int)status_words().size() || !word) return -1;
     unsigned w = 0;

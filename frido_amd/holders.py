@@ -25,6 +25,13 @@ class Conv(nn.Module):
         self.bias = _p(cout)
 
 
+class Conv1(nn.Module):   # nn.Conv1d, kernel 1: (cout, cin, 1)
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.weight = _p(cout, cin, 1)
+        self.bias = _p(cout)
+
+
 class ConvT(nn.Module):   # nn.ConvTranspose2d layout: (cin, cout, k, k)
     def __init__(self, cin, cout, k):
         super().__init__()
@@ -124,6 +131,14 @@ class SpatialTransformerP(nn.Module):   # attention.py:250-280
         self.proj_out = Conv(c, c, 1)
 
 
+class AttentionBlockP(nn.Module):   # pyunet.py:303-340
+    def __init__(self, c, cond_c, spade):
+        super().__init__()
+        self.norm = _norm(c, cond_c, spade)
+        self.qkv = Conv1(c, 3 * c)
+        self.proj_out = Conv1(c, c)
+
+
 class DownP(nn.Module):
     def __init__(self, c):
         super().__init__()
@@ -141,6 +156,8 @@ def _make(b, a):
         return ResBlockP(b.cin, b.cout, a.time_embed_dim, a.model_channels, a.use_spade)
     if b.kind == "st":
         return SpatialTransformerP(b.cin, a.model_channels, a.context_dim, a.use_spade, a.transformer_depth)
+    if b.kind == "attn":
+        return AttentionBlockP(b.cin, a.model_channels, a.use_spade)
     if b.kind == "down":
         return DownP(b.cin)
     if b.kind == "up":
@@ -153,6 +170,8 @@ def build_unet_params(root: nn.Module, cfg):
     a = unet_arch(cfg)
     mc, te = a.model_channels, a.time_embed_dim
     root.time_embed = seq(Lin(mc, te), Nop(), Lin(te, te))
+    if a.num_classes is not None:      # pyunet.py:567-571
+        root.label_emb = Emb(a.num_classes, te) if a.use_embed else Lin(a.num_classes, te)
     if a.num_stage > 1:
         root.stage_emb = Emb(a.num_stage, te)
     if a.use_split_head:

@@ -105,12 +105,23 @@ class PyUNetModel(_Versioned, nn.Module):
             assert context_dim is not None, "context_dim is required with use_spatial_transformer"
         if num_heads == -1:
             assert num_head_channels != -1, "Either num_heads or num_head_channels has to be set"
-        unsupported = dict(num_classes=num_classes, use_pos_embed=use_pos_embed, use_mscond=use_mscond,
-                           use_stage_expert=use_stage_expert, n_embed=n_embed, resblock_updown=resblock_updown,
-                           use_scale_shift_norm=use_scale_shift_norm)
+        if context_dim is not None:
+            assert use_spatial_transformer, "context_dim needs use_spatial_transformer (pyunet.py:516-517)"
+        if num_head_channels == -1:
+            assert num_heads != -1, "Either num_heads or num_head_channels has to be set"
+        unsupported = dict(use_pos_embed=use_pos_embed, use_mscond=use_mscond, use_stage_expert=use_stage_expert, n_embed=n_embed,
+                           resblock_updown=resblock_updown, use_scale_shift_norm=use_scale_shift_norm)
         bad = [k for k, v in unsupported.items() if v]
-        if bad or dims != 2 or not legacy or not conv_resample:
-            raise NotImplementedError(f"PyUNetModel options not used by any shipped Frido config: {bad}")
+        if dims != 2:
+            bad.append("dims != 2")
+        if not conv_resample:
+            bad.append("conv_resample=False")
+        if use_spatial_transformer and not legacy:
+            bad.append("legacy=False with use_spatial_transformer=True (multi-head SpatialTransformer)")
+        if use_spatial_transformer and num_classes is not None:
+            bad.append("num_classes with use_spatial_transformer=True")
+        if bad:
+            raise NotImplementedError(f"PyUNetModel options that are not built: {bad}")
         if use_split_head:
             assert len(split_embed_dim_list) != 0 and sum(split_embed_dim_list) == in_channels
         self.cfg = dict(image_size=image_size, in_channels=in_channels, model_channels=model_channels,
@@ -119,7 +130,9 @@ class PyUNetModel(_Versioned, nn.Module):
                         num_head_channels=num_head_channels, num_heads=num_heads,
                         use_spatial_transformer=use_spatial_transformer, transformer_depth=transformer_depth,
                         context_dim=context_dim, num_stage=num_stage, use_split_head=use_split_head,
-                        split_embed_dim_list=list(split_embed_dim_list), use_SPADE_norm=use_SPADE_norm)
+                        split_embed_dim_list=list(split_embed_dim_list), use_SPADE_norm=use_SPADE_norm,
+                        num_heads_upsample=num_heads_upsample, legacy=legacy, use_new_attention_order=use_new_attention_order,
+                        num_classes=num_classes, use_embed=use_embed)
         self.image_size, self.in_channels, self.model_channels, self.out_channels = image_size, in_channels, model_channels, out_channels
         self.num_res_blocks, self.attention_resolutions, self.dropout = num_res_blocks, attention_resolutions, dropout
         self.channel_mult, self.conv_resample, self.num_classes = channel_mult, conv_resample, num_classes
@@ -127,6 +140,7 @@ class PyUNetModel(_Versioned, nn.Module):
         self.num_heads, self.num_head_channels, self.num_heads_upsample = num_heads, num_head_channels, num_heads_upsample
         self.predict_codebook_ids = False
         self.num_stage, self.use_split_head = num_stage, use_split_head
+        self.use_embed, self.use_spatial_transformer = use_embed, use_spatial_transformer
         self.split_embed_dim_list, self.use_SPADE_norm = list(split_embed_dim_list), use_SPADE_norm
         self.precision = precision
         self.arch = holders.build_unet_params(self, self.cfg)
@@ -144,17 +158,28 @@ class PyUNetModel(_Versioned, nn.Module):
         return self._rt
 
     def forward(self, x, timesteps=None, context=None, y=None, stage=None, **kwargs):
-        if y is not None:      # pyunet.py:877-879 asserts (y is not None) == (num_classes is not None); class-conditional denoisers are not built (arch.py)
-            raise NotImplementedError("class-conditional denoiser (num_classes / conditioning_key='adm'): no shipped Frido config uses it")
-        if context is None:
+        # pyunet.py:877-879 asserts (y is not None) == (num_classes is not None)
+        if y is not None and self.num_classes is None:
+            raise NotImplementedError("class-conditional denoiser (num_classes / conditioning_key='adm'): this model was built without num_classes, "
+                                      "so it takes no y")
+        if y is None and self.num_classes is not None:
+            raise ValueError("must specify y if and only if the model is class-conditional (pyunet.py:877-879)")
+        if self.use_spatial_transformer and context is None:
             raise NotImplementedError("PyUNetModel.forward without a context: the reference's SpatialTransformer then attends to its own input "
                                       "(attention.py:171 `default(context, x)`); every shipped Frido config passes one, that plan is not built")
+        if not self.use_spatial_transformer:
+            context = None      # the AttentionBlock family ignores it (TimestepEmbedSequential, pyunet.py:81-91)
+        if y is not None:
+            if self.use_embed:
+                assert y.shape == (x.shape[0],), "y: one class index per sample (pyunet.py:887)"
+            else:
+                assert y.shape == (x.shape[0], self.num_classes), "y: [B, num_classes] for the Linear label embedding"
         if not x.is_cuda:
             _no_cpu("PyUNetModel.forward", x.device)
         if self.num_stage > 1 and not isinstance(stage, int):
             stage = int(stage)
         from . import autoplanes
-        return autoplanes.run(self, lambda _n: self.runtime().forward(x, timesteps, context, stage), "PyUNetModel.forward")
+        return autoplanes.run(self, lambda _n: self.runtime().forward(x, timesteps, context, stage, y=y), "PyUNetModel.forward")
 
 
 UNetModel = PyUNetModel   # `ldm.modules.diffusionmodules.openaimodel.UNetModel` alias used by two shipped configs
@@ -482,7 +507,8 @@ class DiffusionWrapper(_Base):
     def forward(self, x, t, c_concat: list = None, c_crossattn: list = None, stage=None):
         """frido.py:1635-1654, key for key.  Every shipped config uses 'crossattn'; 'hybrid' (channel concat + context) runs on the same
         denoiser plan; None / 'concat' reach a denoiser WITHOUT a context, 'adm' one with class labels -- the denoiser says which of
-        those it was built for (PyUNetModel.forward raises NotImplementedError for a context-free SpatialTransformer and for `y`)."""
+        those it was built for: an AttentionBlock denoiser (use_spatial_transformer=False) runs without a context and, built with num_classes, takes
+        `y`; PyUNetModel.forward raises NotImplementedError for a context-free SpatialTransformer and for `y` on a model without num_classes."""
         key = self.conditioning_key
         if key is None:
             return self.diffusion_model(x, t, stage=stage)

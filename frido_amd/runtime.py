@@ -56,10 +56,11 @@ class DenoiserRuntime:
         return self._replicas[replica]
 
     @_lib.with_planes
-    def forward(self, x, t, context, stage):
-        """x (B, Cin, H, W) f32 cuda NCHW, t (B,) int64, context (B, nctx, cd) -> eps (B, nch, H, W)."""
+    def forward(self, x, t, context, stage, y=None):
+        """x (B, Cin, H, W) f32 cuda NCHW, t (B,) int64, context (B, nctx, cd) or None (AttentionBlock denoisers), y class labels
+        ((B,) int64 or (B, num_classes) float) or None -> eps (B, nch, H, W)."""
         B, Cin, H, W = x.shape
-        nctx = context.shape[1]
+        nctx = context.shape[1] if context is not None else 0
         stage = 0 if stage is None else int(stage)
         key = (B, H, W, nctx, stage, Cin)
         st = current_stream_ptr(self.device)
@@ -71,7 +72,10 @@ class DenoiserRuntime:
         xc = x.contiguous().float()
         _run1(self.b, "FRIDO_OP_RELAYOUT", st, src=xc.data_ptr(), dst=plan.x_state.data_ptr(), B=B, HW=H * W, Csrc=Cin,
               c0=0, Cuse=Cin, Cdst=Cin, d0=0, to_nchw=0)
-        plan.set_context(context.to(torch.float32))
+        if context is not None:
+            plan.set_context(context.to(torch.float32))
+        if y is not None:
+            plan.set_labels(y)
         plan.set_timesteps(t.to(torch.int64))
         plan.pre.run(st)
         plan.step.run(st)
@@ -105,6 +109,9 @@ class SamplerEngine:
         self.n_steps = tab.shape[0]
         self.coef = torch.from_numpy(tab).to(self.dev)
         self.step = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        # class-conditional denoisers: the embedding table has one row per (step, sample); this counter advances by Bx per step
+        self.labels = cfg.get("num_classes") is not None
+        self.step_bx = torch.zeros(1, dtype=torch.int32, device=self.dev) if self.labels else None
         self.rng = torch.zeros(2, dtype=torch.int64, device=self.dev)   # {seed, sample0} read by the captured kernels
         self.cfg_dev = torch.ones(1, dtype=torch.float32, device=self.dev)   # guidance scale read by the captured kernels
         if not cfg.get("use_split_head", False):
@@ -116,7 +123,8 @@ class SamplerEngine:
         with self.b.persist_scope() as owned:       # this engine owns its plans' persistent buffers: evicting it frees them
             for s in range(self.num_stage):
                 plan = UNetStagePlan(self.b, cfg, B=B, H=H, W=W, nctx=nctx, stage=s, x_state=self.x, temb_rows=self.n_steps,
-                                     per_sample_t=False, step_ptr=self.step.data_ptr(), xrep=self.xrep)
+                                     per_sample_t=False, step_ptr=self.step.data_ptr(), xrep=self.xrep,
+                                     step_bx_ptr=self.step_bx.data_ptr() if self.labels else None)
                 self.stages.append(plan)
         self._persist = owned
         self.graphs = {}
@@ -134,6 +142,12 @@ class SamplerEngine:
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=self.dev)
         return self._stream
+
+    def _step_add(self, prog, delta):
+        """Advance the device step counter (and, for a class-conditional denoiser, the per-sample table counter by delta * Bx)."""
+        prog.emit("FRIDO_OP_STEP_ADD", step=self.step.data_ptr(), delta=delta)
+        if self.labels:
+            prog.emit("FRIDO_OP_STEP_ADD", step=self.step_bx.data_ptr(), delta=delta * self.B * self.xrep)
 
     def _sampler_op(self, s, *, noise_ptr, noise_C, seed, sample0, write_x=1, x_out=None, eps_out=None, hist=(),
                     row_offset=0, hist_mode=0, no_cfg=False):
@@ -200,9 +214,11 @@ class SamplerEngine:
         elif callable(noise):
             draw = noise
         with torch.cuda.stream(stream):
-            ctx = cond.to(self.dev, torch.float32)
+            # cond: the cross-attention context (SpatialTransformer denoisers), class labels (class-conditional ones) or None
+            ctx = cond.to(self.dev, torch.float32 if not self.labels or cond.is_floating_point() else torch.int64) if cond is not None else None
             if self.xrep == 2:
-                ctx = torch.cat([ctx, uncond.to(self.dev, torch.float32)], dim=0)
+                assert ctx is not None, "classifier-free guidance needs a conditioning"
+                ctx = torch.cat([ctx, uncond.to(self.dev, ctx.dtype)], dim=0)
             self.cfg_dev.fill_(self.cfg_scale)
             # ---- x_T (ddim.py:127-130) ----
             if x_T is not None:
@@ -227,9 +243,14 @@ class SamplerEngine:
                     continue                 # ddim.py:150-152: "Auto adopt x_T into stage 0" (no denoising, no hand-off)
                 plan = self.stages[s]
                 Cs = sum(self.embed[:s + 1])
-                plan.set_context(ctx)
+                if self.labels:
+                    plan.set_labels(ctx)
+                elif ctx is not None:
+                    plan.set_context(ctx)
                 plan.set_timesteps(t_loop)
                 self.step.zero_()
+                if self.labels:
+                    self.step_bx.zero_()
                 plan.pre.run(sp)
                 if self.kind == "ddim":
                     self._ddim_stage(s, sp, draw, seed, sample0, inter, log_every_t, callback, img_callback, Cs)
@@ -291,7 +312,7 @@ class SamplerEngine:
                 body = Prog(self.dev, self.b.nsplit)
                 body.ops = list(plan.step.ops)
                 body.emit("FRIDO_OP_SAMPLER_STEP", **self._sampler_op(s, noise_ptr=noise_ptr, noise_C=noise_C, seed=0, sample0=0))
-                body.emit("FRIDO_OP_STEP_ADD", step=self.step.data_ptr(), delta=1)
+                self._step_add(body, 1)
                 body.keep = [plan]
                 self.graphs[key] = body.capture(sp) if self.use_graph else body
             g = self.graphs[key]
@@ -303,7 +324,7 @@ class SamplerEngine:
                 full = Prog(self.dev, self.b.nsplit)
                 full.ops = list(plan.step.ops)
                 full.emit("FRIDO_OP_SAMPLER_STEP", **self._sampler_op(s, noise_ptr=None, noise_C=0, seed=0, sample0=0))
-                full.emit("FRIDO_OP_STEP_ADD", step=self.step.data_ptr(), delta=1)
+                self._step_add(full, 1)
                 full.keep = [plan]
                 self.graphs[key] = full.capture(sp) if self.use_graph else full
             g = self.graphs[key]
@@ -367,7 +388,7 @@ class SamplerEngine:
             self.rng.copy_(torch.tensor([seed, sample0], dtype=torch.int64))
         upd = Prog(self.dev, self.b.nsplit)
         upd.emit("FRIDO_OP_SAMPLER_STEP", **self._sampler_op(s, noise_ptr=noise_ptr, noise_C=noise_C, seed=0, sample0=0, no_cfg=True))
-        upd.emit("FRIDO_OP_STEP_ADD", step=self.step.data_ptr(), delta=1)
+        self._step_add(upd, 1)
         t_steps = self.t_loop.astype(np.int64)
         for i in range(n):
             plan.step.run(sp)
@@ -388,9 +409,12 @@ class SamplerEngine:
         def prog(*ops):
             p = Prog(self.dev, self.b.nsplit)
             for kind, kw in ops:
-                p.emit(kind, **kw)
+                if kind == "step_add":
+                    self._step_add(p, kw)
+                else:
+                    p.emit(kind, **kw)
             return p
-        step_add = lambda d: ("FRIDO_OP_STEP_ADD", dict(step=self.step.data_ptr(), delta=d))
+        step_add = lambda d: ("step_add", d)
         upd = lambda mode: ("FRIDO_OP_SAMPLER_STEP", self._sampler_op(s, noise_ptr=None, noise_C=0, seed=0, sample0=0, hist_mode=mode, no_cfg=True))
         save = ("FRIDO_OP_COPY", dict(src=self.x.data_ptr(), dst=self.x_save.data_ptr(), n=nbytes))
         restore = ("FRIDO_OP_COPY", dict(src=self.x_save.data_ptr(), dst=self.x.data_ptr(), n=nbytes))
@@ -438,15 +462,15 @@ class SamplerEngine:
                 p.emit("FRIDO_OP_COPY", src=self.x.data_ptr(), dst=self.x_save.data_ptr(), n=nbytes)
                 p.emit("FRIDO_OP_SAMPLER_STEP", **self._sampler_op(s, noise_ptr=None, noise_C=0, seed=0, sample0=0, hist_mode=1))
                 if n > 1:
-                    p.emit("FRIDO_OP_STEP_ADD", step=self.step.data_ptr(), delta=1)
+                    self._step_add(p, 1)
                 p.ops += list(plan.step.ops)
                 if n > 1:
-                    p.emit("FRIDO_OP_STEP_ADD", step=self.step.data_ptr(), delta=-1)
+                    self._step_add(p, -1)
                 p.emit("FRIDO_OP_COPY", src=self.x_save.data_ptr(), dst=self.x.data_ptr(), n=nbytes)
                 p.emit("FRIDO_OP_SAMPLER_STEP", **self._sampler_op(s, noise_ptr=None, noise_C=0, seed=0, sample0=0, hist_mode=3))
             else:
                 p.emit("FRIDO_OP_SAMPLER_STEP", **self._sampler_op(s, noise_ptr=None, noise_C=0, seed=0, sample0=0, hist_mode=1))
-            p.emit("FRIDO_OP_STEP_ADD", step=self.step.data_ptr(), delta=1)
+            self._step_add(p, 1)
             p.keep = [plan]
             return p.capture(sp) if self.use_graph else p
 

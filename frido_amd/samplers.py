@@ -53,7 +53,7 @@ class _SamplerBase:
             while len(cache) >= ENGINE_CACHE_SIZE:      # least-recently-used engine goes; it owns its plans' persistent buffers
                 # (Builder.persist_scope) and graphs, so its HBM is released with it -- the activation pool is shared and reused
                 cache.popitem(last=False)
-            cache[key] = SamplerEngine(rt.builder_for(replica), unet.cfg, B=B, C=C, H=H, W=W, nctx=nctx, S=S, eta=eta, kind=self.KIND,
+            cache[key] = SamplerEngine(rt.builder_for(replica), unet.cfg, B=B, C=C, H=H, W=W, nctx=nctx if isinstance(nctx, int) else 0, S=S, eta=eta, kind=self.KIND,
                                        alphas_cumprod=self.model.alphas_cumprod.detach().float().cpu().numpy(),
                                        embed_dim=self.model.embed_dim_list, cfg_scale=scale, num_stage=num_stage,
                                        temperature=temperature)
@@ -75,17 +75,36 @@ class _SamplerBase:
                                       "x0 and the per-stage latent, ddim.py:158-161); not provided on the HIP path")
         if quantize_x0:
             raise NotImplementedError("quantize_x0: the reference calls exit() on this option (ddim.py:251-253)")
-        if conditioning is None or isinstance(conditioning, dict):
-            raise NotImplementedError("cross-attention conditioning tensor required")
-        if conditioning.shape[0] != batch_size:
-            # the reference only prints a warning here (ddim.py:87-93) and then fails (or silently broadcasts) inside the
-            # denoiser; a mismatched batch is never what the caller meant
-            raise ValueError(f"Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
-        if unconditional_conditioning is not None and unconditional_conditioning.shape != conditioning.shape:
-            raise ValueError(f"unconditional_conditioning {tuple(unconditional_conditioning.shape)} must match "
-                             f"conditioning {tuple(conditioning.shape)}")
-        if not conditioning.is_cuda:
-            raise FridoHipError("sample(): conditioning must live on the MI355X (there is no CPU path)")
+        unet = getattr(getattr(self.model, "model", None), "diffusion_model", None)
+        has_ctx = getattr(unet, "use_spatial_transformer", True)
+        labels = getattr(unet, "num_classes", None) is not None
+        if isinstance(conditioning, dict):
+            raise NotImplementedError("dict conditionings ('concat' / 'hybrid'): pass the cross-attention conditioning tensor or the class labels")
+        if conditioning is None:
+            if has_ctx:
+                raise NotImplementedError("cross-attention conditioning tensor required")
+            if labels:
+                raise ValueError("a class-conditional denoiser needs its labels as `conditioning`")
+            if unconditional_guidance_scale != 1.:
+                raise ValueError("classifier-free guidance needs a conditioning")
+        else:
+            if not has_ctx and not labels:
+                raise ValueError("this denoiser takes neither a context nor class labels: pass conditioning=None")
+            if conditioning.shape[0] != batch_size:
+                # the reference only prints a warning here (ddim.py:87-93) and then fails (or silently broadcasts) inside the
+                # denoiser; a mismatched batch is never what the caller meant
+                raise ValueError(f"Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
+            if labels:
+                want = (batch_size,) if unet.use_embed else (batch_size, unet.num_classes)
+                if tuple(conditioning.shape) != want:
+                    raise ValueError(f"class labels of shape {tuple(conditioning.shape)}: this denoiser takes {want}")
+            if unconditional_conditioning is not None and unconditional_conditioning.shape != conditioning.shape:
+                raise ValueError(f"unconditional_conditioning {tuple(unconditional_conditioning.shape)} must match "
+                                 f"conditioning {tuple(conditioning.shape)}")
+            if not conditioning.is_cuda:
+                raise FridoHipError("sample(): conditioning must live on the MI355X (there is no CPU path)")
+        # engine-cache key: context length, or which conditioning mode the plans were built for
+        mode = conditioning.shape[1] if has_ctx else ("labels" if labels else "uncond")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         if unconditional_guidance_scale != 1.:
             assert unconditional_conditioning is not None
@@ -96,7 +115,7 @@ class _SamplerBase:
         def go(noise_src):
             # the engine is looked up per attempt: a repeated run (autoplanes: the default plane format saturated) belongs to the
             # denoiser's NEW runtime on the bf16-pair build, with its own plans, buffers and graphs
-            eng = self._engine(batch_size, tuple(shape), conditioning.shape[1], S, eta, unconditional_guidance_scale, num_stage,
+            eng = self._engine(batch_size, tuple(shape), mode, S, eta, unconditional_guidance_scale, num_stage,
                                temperature, replica)
             return eng.run(conditioning, unconditional_conditioning, x_T=x_T, noise=noise_src, seed=seed, sample0=sample0,
                            log_every_t=log_every_t, callback=callback, img_callback=img_callback, noise_dropout=noise_dropout,

@@ -14,7 +14,7 @@ import torch
 
 from .arch import unet_arch
 from .builder import Builder, ACT_NONE, ACT_RELU, ACT_SILU
-from .engine import rup
+from .engine import pack_matrix, rup
 
 import os
 CHAIN_FF = os.environ.get("FRIDO_CHAIN_FF", "1") != "0"     # FF2 + proj_out of a transformer block as one GEMM (A/B switch)
@@ -33,10 +33,12 @@ class _Shape:
 
 class UNetStagePlan:
     def __init__(self, b: Builder, cfg, *, B, H, W, nctx, stage, x_state, temb_rows, per_sample_t, step_ptr=None,
-                 xrep=1):
+                 xrep=1, step_bx_ptr=None):
         """x_state: f32 device tensor [B][H*W][Ctot] (NHWC latent).  The denoiser runs on a logical batch
         Bx = B * xrep (xrep = 2 for classifier-free guidance: [cond | uncond] share x, differ in context).
-        temb_rows: number of rows of the timestep table (S in sampler mode, Bx when per_sample_t)."""
+        temb_rows: number of rows of the timestep table (S in sampler mode, Bx when per_sample_t).
+        step_bx_ptr (class-conditional denoisers in sampler mode): a second device counter that advances by Bx per step -- the
+        embedding table then has one row per (step, sample), S * Bx in all, and a ResBlock row m reads row m / HW + *step_bx."""
         self.b, self.cfg = b, cfg
         a = self.a = unet_arch(cfg)
         self.B, self.H, self.W, self.nctx, self.stage, self.xrep = B, H, W, nctx, stage, xrep
@@ -45,10 +47,19 @@ class UNetStagePlan:
         self.Ctot = x_state.shape[-1]
         self.per_sample_t = per_sample_t
         self.step_ptr = step_ptr
+        self.step_bx_ptr = step_bx_ptr
+        self.table_per_sample = a.num_classes is not None and not per_sample_t
+        assert not self.table_per_sample or step_bx_ptr, "a class-conditional sampler plan needs the per-sample step counter"
         self.temb_rows = temb_rows
         dev = b.device
         self.t_dev = torch.zeros(temb_rows, dtype=torch.int64, device=dev)
-        self.ctx_in = torch.zeros(self.Bx, nctx, a.context_dim, dtype=torch.float32, device=dev)
+        # cross-attention context: SpatialTransformer denoisers only (the AttentionBlock family has none, pyunet.py:513-517)
+        self.ctx_in = torch.zeros(self.Bx, nctx, a.context_dim, dtype=torch.float32, device=dev) if a.context_dim is not None else None
+        # class labels (pyunet.py:885-888): one per logical sample -- int64 indices (nn.Embedding) or float rows (nn.Linear)
+        self.y_in = None
+        if a.num_classes is not None:
+            self.y_in = (torch.zeros(self.Bx, dtype=torch.int64, device=dev) if a.use_embed
+                         else torch.zeros(self.Bx, a.num_classes, dtype=torch.float32, device=dev))
         self.nch = a.splits[stage] if a.use_split_head else cfg["out_channels"]
         self.eps = torch.zeros(self.Bx * H * W, self.nch, dtype=torch.float32, device=dev)
         self.c0 = sum(a.splits[:stage]) if (a.use_split_head and a.use_spade) else 0
@@ -60,7 +71,7 @@ class UNetStagePlan:
         self.res_cout = [blk.cout for grp in (a.input_blocks + [a.middle] + a.output_blocks) for blk in grp
                          if blk.kind == "res"]
         self.res_off = np.concatenate([[0], np.cumsum(self.res_cout)]).astype(int)
-        self.E = b.persistent_f32(temb_rows, int(self.res_off[-1]))
+        self.E = b.persistent_f32(temb_rows * (self.Bx if self.table_per_sample else 1), int(self.res_off[-1]))
         self.kv = {}        # ST prefix -> (k operand [Bx*nctx][C], vT operand [Bx][C][nctx_pad])
         self.spade = {}     # SPADE module prefix -> (gamma F32-like, beta)
         self.pre = self._build_pre()
@@ -116,7 +127,10 @@ class UNetStagePlan:
             bias2 = bias2 + b.w["stage_emb.weight"][self.stage].float()
         bias2 = bias2.contiguous()
         b._persist.append(bias2)
-        semb = b.linear(h1, "time_embed.2", bias_ptr=bias2.data_ptr(), act=ACT_SILU, out="op")   # SiLU(emb)
+        if a.num_classes is None:
+            semb = b.linear(h1, "time_embed.2", bias_ptr=bias2.data_ptr(), act=ACT_SILU, out="op")   # SiLU(emb)
+        else:
+            semb = self._label_semb(h1, bias2, n)
         h1.free()
         wcat = b.cat_lin_weight("emb_cat", [f"{p}.emb_layers.1.weight" for p in self.res_names])
         bcat = torch.cat([b.w[f"{p}.emb_layers.1.bias"].float() for p in self.res_names]).contiguous()
@@ -124,10 +138,10 @@ class UNetStagePlan:
         b.linear(semb, None, wop=wcat, bias_ptr=bcat.data_ptr(), out=("f32", self._T(self.E)))
         semb.free()
         # ---- cross-attention K / V^T of the context (attention.py:175-176), once per sample ----
-        ctx_op = b.pack(self.ctx_in.data_ptr(), 1, self.Bx * self.nctx, a.context_dim, 0, a.context_dim)
+        ctx_op = b.pack(self.ctx_in.data_ptr(), 1, self.Bx * self.nctx, a.context_dim, 0, a.context_dim) if self.ctx_in is not None else None
         for grp in a.input_blocks + [a.middle] + a.output_blocks:
             for blk in grp:
-                if blk.kind != "st":
+                if blk.kind != "st" or ctx_op is None:
                     continue
                 for dpt in range(a.transformer_depth):
                     t = f"{blk.prefix}.transformer_blocks.{dpt}.attn2"
@@ -141,7 +155,8 @@ class UNetStagePlan:
                         for o_ in (k, vT):      # zero the residual planes: the cache then carries 8 mantissa bits
                             prog.emit("FRIDO_OP_FILL", dst=o_.ptr + 2 * o_.lo, n=o_.lo // 2, value=0)
                     self.kv[(blk.prefix, dpt)] = (k, vT, bvo)
-        ctx_op.free()
+        if ctx_op is not None:
+            ctx_op.free()
         # ---- SPADE conditioning (spade_norm.py:44-60), timestep-invariant within a stage ----
         if self.spade_on:
             HW = self.H * self.W
@@ -168,7 +183,7 @@ class UNetStagePlan:
             for blk in grp:
                 if blk.kind == "res":
                     out += [(blk.prefix + ".in_layers.0", blk.cin, lvl), (blk.prefix + ".out_layers.0", blk.cout, lvl)]
-                elif blk.kind == "st":
+                elif blk.kind in ("st", "attn"):
                     out.append((blk.prefix + ".norm", blk.cin, lvl))
                 elif blk.kind == "down":
                     lvl += 1
@@ -181,7 +196,7 @@ class UNetStagePlan:
             for blk in grp:
                 if blk.kind == "res":
                     out += [(blk.prefix + ".in_layers.0", blk.cin, lvl), (blk.prefix + ".out_layers.0", blk.cout, lvl)]
-                elif blk.kind == "st":
+                elif blk.kind in ("st", "attn"):
                     out.append((blk.prefix + ".norm", blk.cin, lvl))
                 elif blk.kind == "up":
                     lvl -= 1
@@ -201,6 +216,9 @@ class UNetStagePlan:
         d = dict(ptr=self.E.data_ptr() + 4 * int(self.res_off[ridx]), ld=int(self.res_off[-1]))
         if self.per_sample_t:
             d["rows_per_vec"] = None     # filled by caller (HW at that resolution)
+        elif self.table_per_sample:
+            d["rows_per_vec"] = None     # row (step, sample) = m / HW + step * Bx
+            d["step"] = self.step_bx_ptr
         else:
             d["rows_per_vec"] = 1 << 30  # every row uses the row selected by the step counter
             d["step"] = self.step_ptr
@@ -341,6 +359,79 @@ class UNetStagePlan:
         h4.free()
         return out
 
+    def _attention_block(self, blk, x, h, w):
+        """AttentionBlock._forward (pyunet.py:346-358): norm -> qkv (1x1) -> QKVAttention[Legacy] over blk.heads heads -> proj_out + x."""
+        b, HW, C, Bx = self.b, h * w, blk.cin, self.Bx
+        pre, heads = blk.prefix, blk.heads
+        d = C // heads
+        a0, _ = self._norm(x, None, HW, pre + ".norm", 1e-5, ACT_NONE)
+        if (C, HW) not in self._vt_self:
+            self._vt_self[(C, HW)] = b.persistent_op(C, rup(HW, 32), batch=Bx, zero=True)
+        vT = self._vt_self[(C, HW)]
+        # V rows of the qkv weight, head-major (head h = rows h d ..): 3 d h + 2 d + j after a heads-first split (QKVAttentionLegacy,
+        # pyunet.py:399), 2 C + h d + j after a qkv-first split (QKVAttention, :431).  One head: 2 C .. in both.
+        hh, jj = torch.arange(heads)[:, None], torch.arange(d)[None, :]
+        vrows = ((2 * C + hh * d + jj) if (blk.new_order or heads == 1) else (3 * d * hh + 2 * d + jj)).flatten()
+        key = ("attn_v", pre, heads == 1)
+        if key not in b._wcache:
+            wqkv, bqkv = b.h64(pre + ".qkv.weight"), b.h64(pre + ".qkv.bias")
+            wv, bv = wqkv[vrows], bqkv[vrows]
+            if heads == 1:      # W_o (P (X W_v^T + b_v)) + b_o = P (X (W_o W_v)^T) + (W_o b_v + b_o): the rows of P sum to one
+                wo = b.h64(pre + ".proj_out.weight")
+                wv, bv = wo @ wv, wo @ bv + b.h64(pre + ".proj_out.bias")
+            b._wcache[key] = (pack_matrix(b.to_dev(wv), b.nsplit), b.to_dev(bv))
+        wv_op, bv_dev = b._wcache[key]
+        # V^T and the q / k projection both read a0 and are independent: V^T goes to the executor's side stream
+        b.prog.sync(0, 1)
+        with b.prog.side():
+            b.v_transposed(a0, C, wv_op, Bx, HW, C, bias_ptr=None if heads == 1 else bv_dev.data_ptr(), out=vT)
+        if heads == 1:
+            # one head, any width: q | k = the first 2 C rows of the projection, the existing single-head kernels, proj_out folded
+            # into V so that P V + bias + x lands on the residual stream
+            qk = b.linear(a0, None, wop=b.lin_weight(pre + ".qkv.weight", rows=(0, 2 * C)), bias_ptr=b.bias(pre + ".qkv.bias"), out="op")
+            b.prog.sync(1, 0)
+            out = b.attention(qk, 2 * C, qk, 2 * C, vT, Bx, HW, HW, C, q_off=0, k_off=C, bias_ptr=bv_dev.data_ptr(), residual=x, stream=True)
+            qk.free()
+            a0.free()
+            return out
+        qkv = b.linear(a0, pre + ".qkv", out="op")            # [Bx*HW][3 C]: q and k stay where the projection left them
+        b.prog.sync(1, 0)
+        o = b.attention_heads(qkv, 3 * C, vT, Bx, HW, heads, d, legacy=not blk.new_order)
+        qkv.free()
+        a0.free()
+        out = b.linear(o, pre + ".proj_out", residual=x)
+        o.free()
+        return out
+
+    def _label_semb(self, h1, bias2, n):
+        """SiLU(time_embed(t_emb) + label_emb(y) [+ stage_emb]) as an operand (pyunet.py:883-896 + the SiLU of every emb_layers).
+        The label embedding L [Bx][te] is computed first (a row gather for nn.Embedding, a small GEMM for nn.Linear) and enters the
+        time_embed.2 GEMM as its row vector -- inside the activation, where the reference adds it.
+        Forward mode (n == Bx rows, one timestep per sample): row m takes L[m].
+        Sampler mode (n == S rows, one per step): the table gets S * Bx rows, row i * Bx + z = (step i, sample z): one S-row GEMM per
+        sample z with L[z] as a launch-wide vector, written with a row stride of Bx rows."""
+        b, a, Bx = self.b, self.a, self.Bx
+        te = a.time_embed_dim
+        if a.use_embed:
+            L = b.f32_strict(Bx, te)
+            b.prog.emit("FRIDO_OP_EMBED", tokens=self.y_in.data_ptr(), tok=b.dev_f32("label_emb.weight").data_ptr(), pos=None, out=L.ptr,
+                        rows=Bx, n=Bx, D=te, vocab=a.num_classes)
+        else:
+            y_op = b.pack(self.y_in.data_ptr(), 1, Bx, a.num_classes, 0, a.num_classes)
+            L = b.linear(y_op, "label_emb", out="f32_strict")
+            y_op.free()
+        wop = b.lin_weight("time_embed.2.weight")
+        if self.per_sample_t:
+            semb = b.linear(h1, "time_embed.2", bias_ptr=bias2.data_ptr(), act=ACT_SILU, out="op",
+                            rowvec=dict(ptr=L.ptr, rows_per_vec=1, ld=te))
+        else:
+            semb = b.op(n * Bx, te)
+            for z in range(Bx):
+                b.prog.gemm(n, te, wop.K, h1, wop, bias=bias2.data_ptr(), rowvec=L.ptr + 4 * z * te, rows_per_vec=1 << 30, ldv=te,
+                            act=ACT_SILU, out_op=semb.ptr + 2 * z * te, ldoo=Bx * te, oo_lo=semb.lo)
+        L.free()
+        return semb
+
     def _build_step(self):
         b, a = self.b, self.a
         prog = b.new_prog()
@@ -363,6 +454,8 @@ class UNetStagePlan:
                     ridx += 1
                 elif blk.kind == "st":
                     nxt = self._spatial_transformer(blk, cur, h, w)
+                elif blk.kind == "attn":
+                    nxt = self._attention_block(blk, cur, h, w)
                 elif blk.kind == "down":
                     xo = b.to_operand(cur)
                     nxt = b.conv(xo, self.Bx, h, w, blk.prefix + ".op", stride=2, pad=1)
@@ -378,6 +471,8 @@ class UNetStagePlan:
             if blk.kind == "res":
                 nxt = self._res_block(blk, cur, None, h, w, ridx)
                 ridx += 1
+            elif blk.kind == "attn":
+                nxt = self._attention_block(blk, cur, h, w)
             else:
                 nxt = self._spatial_transformer(blk, cur, h, w)
             if cur is not mid_in:
@@ -393,6 +488,8 @@ class UNetStagePlan:
                     ridx += 1
                 elif blk.kind == "st":
                     nxt = self._spatial_transformer(blk, cur, h, w)
+                elif blk.kind == "attn":
+                    nxt = self._attention_block(blk, cur, h, w)
                 elif blk.kind == "up":
                     xo = b.to_operand(cur)
                     nxt = b.upsample_conv(xo, self.Bx, h, w, blk.prefix + ".conv")
@@ -421,6 +518,10 @@ class UNetStagePlan:
     def set_context(self, ctx):
         """ctx: device f32 [Bx][nctx][context_dim]."""
         self.ctx_in.copy_(ctx)
+
+    def set_labels(self, y):
+        """y: class labels of the Bx logical samples, int64 [Bx] (nn.Embedding) or float [Bx][num_classes] (nn.Linear)."""
+        self.y_in.copy_(y.to(self.y_in.device, self.y_in.dtype))
 
     def set_timesteps(self, t):
         self.t_dev.copy_(t)

@@ -39,8 +39,9 @@ typedef uint16_t frido_bf16;
  * operands became fp16 pairs (frido_x3_plane_format() == 1).  3 (r04): FridoGemm grew at its END (out_u8 / ldu8 / u8_mode, the fused
  * GroupNorm-apply input gn_*), two-plane operand producers saturate at +-65504.  4 (r04): FridoGemm.sk_mode 2 + FridoGnApply.sk_* at the
  * struct's END (a split-K GEMM's reduction finished by the GroupNorm launch that consumes its output).  5 (r05): FridoAttnSmall.skip_act_store
- * at the struct's END; frido_status_flags(&word, clear) (sticky saturation / non-finite flags; clear = 1 resets them). */
-#define FRIDO_ABI_VERSION 6
+ * at the struct's END; frido_status_flags(&word, clear) (sticky saturation / non-finite flags; clear = 1 resets them).
+ * 7: the multi-head flash attention descriptor FridoAttnMh, its launcher frido_attn_mh and the op kind FRIDO_OP_ATTN_MH were ADDED (no existing struct moved). */
+#define FRIDO_ABI_VERSION 7
 #define FRIDO_SPLITK_HEADER_BYTES 65536     /* the ticket header at the start of a split-K workspace; partial sums follow: [splitk][M][N] f32 */
 
 #define FRIDO_OK 0
@@ -262,6 +263,30 @@ typedef struct FridoAttnSmall {
     int32_t skip_act_store;
 } FridoAttnSmall;
 
+/* Multi-head flash attention for SMALL head dimensions (d = 32 or 64; frido_attn_mh_supported): per sample b and head h
+ *     O_h = softmax(alpha * Q_h K_h^T) V_h
+ * with an online softmax over 32-key groups -- the [Nq][Nk] score matrix is never formed.  The attention core of the
+ * reference's AttentionBlock (frido/modules/diffusionmodules/pyunet.py:303-358, QKVAttentionLegacy / QKVAttention 381-440:
+ * num_head_channels = 32 gives 12 / 18 / 30 heads on the 32x32 / 16x16 / 8x8 planes of the f8f4 denoiser); the caller passes
+ * alpha = d ** -0.5 (the reference scales q and k by d ** -0.25 each).  q, k and v stay where the qkv projection left them:
+ *   Q rows [B*Nq] (row stride ldq), head h at columns h * q_hs .. + d of the row that Q points at;
+ *   K rows [B][Nk] (per-sample stride k_bs elements, row stride ldk), head h at columns h * k_hs .. + d;
+ *   VT = V transposed [B][heads * d][ldvt] (per-sample stride vt_bs), head h = rows h * d .., zero columns beyond Nk,
+ *        ldvt >= Nk rounded up to 32;
+ *   O operand rows [B*Nq] (ldo), head h at columns h * d .. + d -- the a.reshape(bs, -1, length) of both reference head orders.
+ * The two orders differ only in the offsets over one qkv operand [B*N][3C]: legacy (pyunet.py:393-396) q / k at columns 0 / d with
+ * q_hs = k_hs = 3 d (v rows 3 d h + 2 d .. of the weight); new order (:427-432) q / k at columns 0 / C with q_hs = k_hs = d.
+ * Any Nq, any Nk (ragged tiles are masked); row strides, head strides and plane offsets keep 16-byte alignment (multiples of 8
+ * elements).  The output goes through the library's plane producers: fp16 planes saturate at +-65504 and raise
+ * FRIDO_STATUS_SATURATED, non-finite softmax statistics raise FRIDO_STATUS_NONFINITE. */
+typedef struct FridoAttnMh {
+    const frido_bf16* Q; int64_t q_lo; int32_t ldq, q_hs;
+    const frido_bf16* K; int64_t k_lo; int64_t k_bs; int32_t ldk, k_hs;
+    const frido_bf16* VT; int64_t vt_lo; int64_t vt_bs; int32_t ldvt;
+    frido_bf16* out_op; int64_t out_lo; int32_t ldo;
+    int32_t B, heads, Nq, Nk, d, nsplit; float alpha;
+} FridoAttnMh;
+
 /* GEGLU gate (attention.py:42-44): x[rows][2H] f32 -> operand [rows][H] = x[:, :H] * gelu_erf(x[:, H:]). */
 typedef struct FridoGeglu {
     const float* x; int32_t rows, H;
@@ -389,7 +414,7 @@ typedef struct FridoSync { int32_t from, to; } FridoSync;
 enum FridoOpKind {
     FRIDO_OP_GEMM = 1, FRIDO_OP_GN_STATS, FRIDO_OP_GN_APPLY, FRIDO_OP_LAYERNORM, FRIDO_OP_SOFTMAX,
     FRIDO_OP_GEGLU, FRIDO_OP_PACK, FRIDO_OP_RELAYOUT, FRIDO_OP_VQ, FRIDO_OP_SAMPLER_STEP,
-    FRIDO_OP_HANDOFF, FRIDO_OP_RANDN, FRIDO_OP_STEP_ADD, FRIDO_OP_FILL, FRIDO_OP_TIME_EMB, FRIDO_OP_CONVT, FRIDO_OP_PLACE, FRIDO_OP_EMBED, FRIDO_OP_TO_U8, FRIDO_OP_ATTN_SMALL, FRIDO_OP_GN_FUSED, FRIDO_OP_COPY, FRIDO_OP_ATTN_FLASH, FRIDO_OP_SYNC, FRIDO_OP_L2NORM, FRIDO_OP__COUNT
+    FRIDO_OP_HANDOFF, FRIDO_OP_RANDN, FRIDO_OP_STEP_ADD, FRIDO_OP_FILL, FRIDO_OP_TIME_EMB, FRIDO_OP_CONVT, FRIDO_OP_PLACE, FRIDO_OP_EMBED, FRIDO_OP_TO_U8, FRIDO_OP_ATTN_SMALL, FRIDO_OP_GN_FUSED, FRIDO_OP_COPY, FRIDO_OP_ATTN_FLASH, FRIDO_OP_SYNC, FRIDO_OP_L2NORM, FRIDO_OP_ATTN_MH, FRIDO_OP__COUNT
 };
 
 /* A program is an array of tagged ops executed in order on one stream by the native executor. */
@@ -399,7 +424,7 @@ typedef struct FridoOp {
         FridoGemm gemm; FridoGnStats gn_stats; FridoGnApply gn_apply; FridoLayerNorm layernorm;
         FridoSoftmax softmax; FridoGeglu geglu; FridoPack pack; FridoRelayout relayout; FridoVq vq;
         FridoSamplerStep sampler_step; FridoHandoff handoff; FridoRandn randn; FridoStepAdd step_add;
-        FridoFill fill; FridoTimeEmb time_emb; FridoConvT convt; FridoPlace place; FridoEmbed embed; FridoToU8 to_u8; FridoAttnSmall attn_small; FridoCopy copy; FridoSync sync; FridoL2Norm l2norm;
+        FridoFill fill; FridoTimeEmb time_emb; FridoConvT convt; FridoPlace place; FridoEmbed embed; FridoToU8 to_u8; FridoAttnSmall attn_small; FridoCopy copy; FridoSync sync; FridoL2Norm l2norm; FridoAttnMh attn_mh;
         char _size[512];
     } u;
 } FridoOp;
@@ -442,6 +467,10 @@ int frido_attn_flash_supported(int32_t d);
 /* (r05) head widths for which a two-plane frido_attn_flash launch may carry FridoAttnSmall.ln_op (its workgroups own whole rows):
  * 256 and 384 always, 512 on the d-split 8-wave form (the default; FRIDO_FLASH_DSPLIT=0 selects the 4-wave form). */
 int frido_attn_flash_ln_supported(int32_t d);
+/* (ABI 7) Multi-head flash attention on a FridoAttnMh descriptor; frido_attn_mh_supported(d) tells whether a head dimension is
+ * instantiated (32 and 64).  Unsupported arguments return FRIDO_EINVAL and launch nothing. */
+int frido_attn_mh(const FridoAttnMh* d, frido_stream_t s);
+int frido_attn_mh_supported(int32_t d);
 /* One-launch GroupNorm (statistics + apply) on a FridoGnApply descriptor whose `partials` is unused; bf16 stream only.
  * frido_gn_fused_chunk returns the channel-chunk width it would use (and the workgroup size), or 0 if the descriptor does
  * not qualify -- then gn_stats + gn_apply is the path. */
@@ -491,7 +520,7 @@ int frido_status_flags(uint32_t* flags, int32_t clear);
  * what the host side calls after a sampling pass / a decode to decide whether the model must move to the bf16-pair planes
  * (frido_amd/models.py auto plane selection); not capturable (it synchronises the stream). */
 int frido_status_poll(frido_stream_t stream, uint32_t* flags, int32_t clear);
-/* diagnostic: the status word of ONE source file of the library (index = link order: igemm, convgn, norm, misc, attn, flash, runtime);
+/* diagnostic: the status word of ONE source file of the library (index = link order: igemm, convgn, norm, misc, attn, flash, flash_mh, runtime);
  * returns -1 past the last one.  tools/find_saturation.py uses it to name the kernel family that raised a bit. */
 int frido_status_word_of(int32_t idx, uint32_t* word);
 int frido_device_info(int32_t* cu_count, int32_t* gcn_arch_is_gfx950, int64_t* hbm_bytes);

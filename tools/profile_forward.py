@@ -39,6 +39,9 @@ def table(prog, sp, title, top=None):
         if n in ("ATTN_SMALL", "ATTN_FLASH"):
             desc = f"B={st.B} Nq={st.Nq} Nk={st.Nk} d={st.d}"
             fl = 4.0 * st.B * st.Nq * st.Nk * st.d
+        if n == "ATTN_MH":
+            desc = f"B={st.B} heads={st.heads} Nq={st.Nq} Nk={st.Nk} d={st.d}"
+            fl = 4.0 * st.B * st.heads * st.Nq * st.Nk * st.d
         if n == "SOFTMAX":
             desc = f"rows={st.rows} N={st.N}"
         rows.append((t, n, desc, fl))
