@@ -148,13 +148,9 @@ __device__ __forceinline__ f32x4 mfma_op(bf16x8 a, bf16x8 b, f32x4 c) {
 // (r06) x * sigmoid(x) with v_rcp_f32 (1 ulp) instead of an IEEE division: the division was 11 of the ~24 VALU instructions per element of
 // every normalise + SiLU + split conversion (tools/cg_prof.py: that conversion is the top-of-step work the fused GroupNorm + conv kernel's
 // matrix pipe waits for; ISA count: 196 -> ~115 instructions per 8-channel unit).  One more ulp on a value that is split into two fp16
-// planes afterwards: 1e-7 relative, two orders below the parity bounds.  -DFRIDO_SILU_DIV=1 restores the division.
-#ifndef FRIDO_SILU_DIV
-#define FRIDO_SILU_DIV 0
-#endif
+// planes afterwards: 1e-7 relative, two orders below the parity bounds.
 __device__ __forceinline__ float silu_f(float v) {
-    if constexpr (FRIDO_SILU_DIV) return v / (1.0f + __expf(-v));
-    else return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
+    return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
 }
 // erf by Abramowitz & Stegun 7.1.26 (|abs error| <= 1.5e-7): one rcp, one exp, six FMAs.  libm's erff costs ~3x as many
 // VALU cycles, and the GEGLU epilogue evaluates it 2e8 times per denoiser forward (it was VALU-, not store-bound).
@@ -162,7 +158,7 @@ __device__ __forceinline__ float erf_fast(float x) {
     const float ax = fabsf(x);
     // (r06) v_rcp_f32: HIP's __frcp_rn is a correctly rounded 1 / x -- the full v_div_scale / v_div_fmas / v_div_fixup sequence, 11 instructions
     // where the approximation's own error (1.5e-7) is 2.5 ulp
-    const float t = FRIDO_SILU_DIV ? __frcp_rn(fmaf(0.3275911f, ax, 1.0f)) : __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
+    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
     float p = fmaf(1.061405429f, t, -1.453152027f);
     p = fmaf(p, t, 1.421413741f);
     p = fmaf(p, t, -0.284496736f);
@@ -172,8 +168,7 @@ __device__ __forceinline__ float erf_fast(float x) {
 }
 // OpenAI CLIP's QuickGELU (clip/model.py): x * sigmoid(1.702 x)
 __device__ __forceinline__ float quickgelu_f(float v) {
-    if constexpr (FRIDO_SILU_DIV) return v / (1.0f + __expf(-1.702f * v));
-    else return v * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * v));
+    return v * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * v));
 }
 __device__ __forceinline__ float gelu_f(float v) { return 0.5f * v * (1.0f + erf_fast(v * 0.70710678118654752f)); }
 

@@ -27,34 +27,12 @@ namespace {
 //
 // LDS (BM = 256): 2 x 49.5 KiB patch + 2 x 24 KiB weights + 7.5 KiB scale / shift table = 154.5 KiB, one workgroup per CU.
 
-// Timing ablations (separate builds, results garbage): 1 = no convert / LDS write of staged units, 2 = no staging loads,
-// 4 = no MFMAs, 8 = no fragment reads, 16 = no weight DMA inside the loop
-#ifndef CG_ABLATE
-#define CG_ABLATE 0
-#endif
-// (r06) 1: the step barrier sits INSIDE the k-step, at the head of its last weight slab (see "mid-step barrier" in the kernel); 0: r04's
-// barrier at the top of every step.  Same MFMAs on the same operands in the same order: bit-identical results.
-#ifndef CG_MIDBAR
-#define CG_MIDBAR 0
-#endif
-// (r06) -DCG_PROF=1 (tools/cg_prof.py; never in the shipped build): every wave of the r04 loop form (CG_MIDBAR=0) sums, over its k-steps,
+// (r06) -DCG_PROF=1 (tools/cg_prof.py; never in the shipped build): every wave sums, over its k-steps,
 // the shader cycles (s_memtime) it spends  [0] waiting for the step's weights (end of the previous step -> arrival at the barrier),
 // [1] inside the barrier, [2] on the weight DMA issue + staging (release -> first fragment address), [3] on fragment reads + MFMAs;
 // [4] = the whole loop, [5] = kernel start -> loop, [6] = epilogue.  Stamps sit where lgkmcnt is 0 anyway (an s_memtime is an SMEM read).
 #ifndef CG_PROF
 #define CG_PROF 0
-#endif
-// (r06) 1: PING-PONG.  The two waves of a SIMD (w and w + 4) run HALF A STEP APART: waves 0-3 own the tile's columns 0-95, waves 4-7 columns
-// 96-191 (so each group streams ITS OWN half of a step's weights and nobody else reads them), group X = waves 0-3 meets at the "A" barriers,
-// group Y at the "B" barriers in between; a group's own barrier is the top of its step (weight DMA issue, staging), the other group's
-// barrier falls between its weight slabs CG_PP_K - 1 and CG_PP_K.  While one wave of a SIMD is in its top-of-step work (800 - 1000 cycles
-// without a single MFMA: tools/cg_prof.py) its partner is in the MFMA half of its own step.  r04 loop form only (CG_MIDBAR 0).
-// Same MFMAs on the same operands in the same order per accumulator: bit-identical results.
-#ifndef CG_PINGPONG
-#define CG_PINGPONG 0
-#endif
-#ifndef CG_PP_K
-#define CG_PP_K 3
 #endif
 
 #if CG_PROF
@@ -152,7 +130,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_kernel(const FridoGemm d) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int wm = CG_PINGPONG ? wave & 3 : wave >> 1, wn = CG_PINGPONG ? wave >> 2 : wave & 1;      // (ping-pong: a SIMD's two waves w, w + 4 = the two column halves of one row block)
+    const int wm = wave >> 1, wn = wave & 1;
 #if CG_PROF
     unsigned cgp[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     const unsigned cgp_t0 = CGP_NOW();
@@ -181,10 +159,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_kernel(const FridoGemm d) {
     float* const tab_sh = tab_sc + MAXC;
 
     // ---- GroupNorm statistics -> per-channel scale / shift table (gn_apply_kernel's prologue: same order, same expressions) ----
-    if constexpr (CG_ABLATE & 64) {       // (timing only) no statistics prologue
-        for (int c = t; c < C; c += NT) { tab_sc[c] = 1.f; tab_sh[c] = 0.f; }
-        __syncthreads();
-    } else
     {
         float* s_mean = reinterpret_cast<float*>(smem);
         float* s_rstd = s_mean + 64;
@@ -274,14 +248,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_kernel(const FridoGemm d) {
     const bool do_silu = d.gn_act == FRIDO_ACT_SILU;
     auto stage_load = [&](auto rc, int c, CgUnit& u) {
         constexpr int r = decltype(rc)::value;
-        if constexpr (CG_ABLATE & 2) { u.x0 = u.x1 = u.g0 = u.g1 = u.b0 = u.b1 = f32x4{0.f, 0.f, 0.f, 0.f}; return; }
         load_unit(c, pix[r] >= 0 ? pix[r] : psafe, u);
     };
     // convert + write round r of chunk c into patch buffer c & 1; YOUNGER = VMEM operations issued after the round's loads
     auto stage_write = [&](auto rc, auto yc, int c, CgUnit& u) {
         constexpr int r = decltype(rc)::value, YOUNGER = decltype(yc)::value;
-        if constexpr (!(CG_ABLATE & 2)) wait_unit<YOUNGER, SPADE>(u);
-        if constexpr (CG_ABLATE & 1) { asm volatile("" ::"v"(u.x0), "v"(u.x1)); return; }
+        wait_unit<YOUNGER, SPADE>(u);
         float sc[8], sh[8];
         {
             const unsigned ta = lds0 + TAB0 + (unsigned)(c * 32 + cu) * 4u;
@@ -338,27 +310,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_kernel(const FridoGemm d) {
     int b_off[3];                                     // element offsets (< 2^31: checked by the launcher)
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
-        int q = wave + 8 * p, plane = q / 12, rc = q - 12 * plane;
-        if constexpr (CG_PINGPONG) {      // this group's column half = chunks 6 wn .. 6 wn + 5 of each plane: twelve chunks on four waves
-            q = (wave & 3) + 4 * p; plane = q / 6; rc = 6 * wn + (q - 6 * plane);
-        }
+        const int q = wave + 8 * p, plane = q / 12, rc = q - 12 * plane;
         const int n = n0 + chan_of_pos(rc * 16 + lrow);               // permuted weight rows: see tile_epilogue
         b_off[p] = (int)((int64_t)plane * d.b_lo + (int64_t)n * d.ldb + lq * 8);
     }
-    bool in_loop = false;
     auto issue_w = [&](int64_t koff, int stage) {
-        if ((CG_ABLATE & 16) && in_loop) return;
-        if constexpr (CG_PINGPONG) {
-            unsigned char* dstp = smem + W0 + stage * WSTAGE;
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                const int q = (wave & 3) + 4 * p, plane = q / 6, rc = 6 * wn + (q - 6 * plane);
-                int bo = b_off[p];
-                asm volatile("" : "+v"(bo));
-                __builtin_amdgcn_global_load_lds((gptr_t)(Bb + koff + bo), (lptr_t)(dstp + plane * WPLANE + rc * 1024), 16, 0, 0);
-            }
-            return;
-        }
         unsigned char* dst = smem + W0 + stage * WSTAGE + wave * 1024;
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
@@ -387,7 +343,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_kernel(const FridoGemm d) {
 
     // one k-step: A fragments from `abase` (a patch buffer or a dense tile, both planes PPLANE apart) at slots sb[i] + shift,
     // weight fragments from stage `ws`; hi*lo + lo*hi + hi*hi per tile, reads in order of first use (the ring kernel's plain loop)
-    auto mma_step = [&](unsigned abase, bool dense, int shift, int ws, auto&& hook, auto&& after) {
+    auto mma_step = [&](unsigned abase, bool dense, int shift, int ws) {
         unsigned aa[TM];
         int s0 = dense ? rb0 : sb0;
         asm volatile("" : "+v"(s0));                   // recomputed per step on purpose: hoisted, the 9 x TM addresses spill
@@ -405,45 +361,24 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_kernel(const FridoGemm d) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                if constexpr (CG_ABLATE & 8) { if (i == 0) fa[p][0] = lds_read128(aa[0] + p * PPLANE); else fa[p][i] = fa[p][0]; }
-                else fa[p][i] = lds_read128(aa[i] + p * PPLANE);
-            }
-        if constexpr (CG_PINGPONG && CG_PP_K == 0) {      // the other group's boundary BEFORE this step's first MFMA: the fragment reads just issued stay in
-            asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(2 + 2 * TM) : "memory");      // flight across it, this wave's patch / tile writes (older) have landed
-            __builtin_amdgcn_s_barrier();
-        }
-        // weight slab j: its fragment was fetched one slab ahead; `hook` runs at the head of the LAST slab (every fragment of the step is
-        // in registers: CG_MIDBAR's barrier), `after(j)` behind slab j's MFMAs (unused in the shipped forms: a hook for experiments)
+            for (int p = 0; p < 2; ++p) fa[p][i] = lds_read128(aa[i] + p * PPLANE);
+        // weight slab j: its fragment was fetched one slab ahead
         static_for<0, TN>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
-#ifdef CG_FAIRPRIO
-            // (A/B, r06) least progress first: a wave's priority falls as it works through the step's weight slabs (2, 2, 1, 1, 0, 0), so the wave
-            // that is behind wins the MFMA arbitration -- age alone lets the older wave of a SIMD finish ~500 cycles early and leaves the younger
-            // one to finish alone, at the ~60 % a lone wave reaches (tools/cg_prof.py)
-            __builtin_amdgcn_s_setprio((TN - 1 - j) >> 1);
-#endif
-            if constexpr (CG_PINGPONG && j == CG_PP_K && CG_PP_K > 0) {      // the OTHER group's step boundary: this slab's weight fragment is the only read in flight
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-            }
             if constexpr (j + 1 < TN) {
 #pragma unroll
                 for (int p = 0; p < 2; ++p) fb[(j + 1) & 1][p] = lds_read128(sbb + p * WPLANE + (j + 1) * 16 * 64);
                 if constexpr (j > 0) asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
             } else {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                hook();
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (CG_ABLATE & 4) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i) asm volatile("" ::"v"(fb[j & 1][0]), "v"(fb[j & 1][1]), "v"(fa[0][i]), "v"(fa[1][i]));
-            } else if constexpr (j == 0) {
+            if constexpr (j == 0) {
                 // first slab: the MFMAs of pixel slabs i0 .. i0 + GI - 1 start as soon as THEIR fragments are back (outstanding after them: the
                 // later slabs' + the prefetched weight fragment).  (r06) inside a group pass-major -- hi*lo of every slab, then lo*hi, then
-                // hi*hi -- so that no MFMA follows one on its own accumulator (igemm_shared.h FRIDO_SLAB0; 0: groups of one = r04's order)
-                constexpr int GI = FRIDO_SLAB0 == 0 ? 1 : (FRIDO_SLAB0 == 2 ? TM : 2);
+                // hi*hi -- so that no MFMA follows one on its own accumulator
+                constexpr int GI = 2;
+                static_assert(TM % 2 == 0, "first-slab MFMAs go in pairs of pixel slabs");
                 static_for<0, TM / GI>([&](auto gc) {
                     constexpr int i0 = decltype(gc)::value * GI;
                     asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(2 * (TM - GI - i0) + 2) : "memory");
@@ -456,45 +391,30 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_kernel(const FridoGemm d) {
                     for (int ii = 0; ii < GI; ++ii) acc[i0 + ii][0] = mfma_op<2>(fb[0][0], fa[0][i0 + ii], acc[i0 + ii][0]);
                     __builtin_amdgcn_sched_barrier(0);
                 });
-            } else if constexpr (FRIDO_SLAB0 != 0) {      // pass-major: a dependent MFMA always has TM - 1 independent ones in front
+            } else {      // pass-major: a dependent MFMA always has TM - 1 independent ones in front
 #pragma unroll
                 for (int i = 0; i < TM; ++i) acc[i][j] = mfma_op<2>(fb[j & 1][0], fa[1][i], acc[i][j]);
 #pragma unroll
                 for (int i = 0; i < TM; ++i) acc[i][j] = mfma_op<2>(fb[j & 1][1], fa[0][i], acc[i][j]);
 #pragma unroll
                 for (int i = 0; i < TM; ++i) acc[i][j] = mfma_op<2>(fb[j & 1][0], fa[0][i], acc[i][j]);
-            } else {
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    acc[i][j] = mfma_op<2>(fb[j & 1][0], fa[1][i], acc[i][j]);
-                    acc[i][j] = mfma_op<2>(fb[j & 1][1], fa[0][i], acc[i][j]);
-                    acc[i][j] = mfma_op<2>(fb[j & 1][0], fa[0][i], acc[i][j]);
-                }
             }
-            after(jc);
             __builtin_amdgcn_sched_barrier(0);
         });
     };
-    auto no_hook = [] {};
-    auto no_after = [](auto) {};
 
-    // ---- prologue: weights of step 0 (mid-step barrier form: and of step 1) in flight, chunk 0 staged without overlap ----
+    // ---- prologue: weights of step 0 in flight, chunk 0 staged without overlap ----
     issue_w((int64_t)cb * 32, cb & 1);
-    if constexpr (CG_MIDBAR) issue_w((int64_t)C + cb * 32, (cb + 1) & 1);      // tap 1 of the first chunk (a slice has >= 9 steps)
     {
         CgUnit pu[NR];                 // every round's loads in flight before the first conversion (the accumulators are not live yet)
         static_for<0, NR>([&](auto rc) { stage_load(rc, cb, pu[decltype(rc)::value]); });
         static_for<0, NR>([&](auto rc) { stage_write(rc, std::integral_constant<int, 0>{}, cb, pu[decltype(rc)::value]); });
     }
 
-    in_loop = true;
 #if CG_PROF
     cgp_prev = CGP_NOW();
     cgp[5] = cgp_prev - cgp_t0;
     const unsigned cgp_loop0 = cgp_prev;
-#endif
-#ifdef CG_PRIO
-    if (wave >= 4) __builtin_amdgcn_s_setprio(1);     // (A/B) static priority for the second-dispatched half: MI355X_MICROARCH.md "Two waves per SIMD" item 4
 #endif
     CgUnit su;                        // the staging round in flight (loaded at an even tap, written at the next odd one)
     CgUnit ru[RU];                    // the raw tile in flight
@@ -531,7 +451,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_kernel(const FridoGemm d) {
 #if CG_PROF
             cgp_a = CGP_NOW(); cgp[0] += cgp_a - cgp_prev;
 #endif
-            if constexpr (!(CG_ABLATE & 128)) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_barrier();
 #if CG_PROF
             cgp_prev = CGP_NOW(); cgp[1] += cgp_prev - cgp_a;
 #endif
@@ -566,7 +486,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_kernel(const FridoGemm d) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             cgp_a = CGP_NOW(); cgp[2] += cgp_a - cgp_prev;
 #endif
-            mma_step(lds0 + (unsigned)((c & 1) * PBUF), false, (T / 3 - 1) * PW + (T % 3 - 1), (c + T) & 1, no_hook, no_after);
+            mma_step(lds0 + (unsigned)((c & 1) * PBUF), false, (T / 3 - 1) * PW + (T % 3 - 1), (c + T) & 1);
 #if CG_PROF
             cgp_prev = CGP_NOW(); cgp[3] += cgp_prev - cgp_a;
 #endif
@@ -575,94 +495,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_kernel(const FridoGemm d) {
             }
         });
     };
-    // ---- (r06) MID-STEP BARRIER form.  r04 met at the TOP of every step (54 - 66 times per launch): after the release a wave first issues
-    // its weight DMA, converts a staging round, computes fragment addresses and waits out an LDS round trip -- with both waves of every SIMD
-    // at the same point, the matrix pipe idles for those few hundred cycles of every ~2700-cycle step.  Here step g's barrier sits at the
-    // head of its LAST weight slab: all of the wave's fragments of the step are in registers (its reads of weight stage g & 1 are over),
-    // TM MFMA triples are ready to issue right after the release, and the top-of-step work of step g + 1 is no longer aligned across waves
-    // (the older wave of a SIMD runs ahead into it while the younger one still issues MFMAs).  Ring protocol (2 weight stages, as before):
-    //   hook of step g:  lgkmcnt(0) [mma_step]; my share of W(g + 1) has landed (vmcnt: only loads issued at THIS step's top are younger);
-    //                    s_barrier  -> W(g + 1) and every patch / raw-tile write before it are published, stage g & 1 is free;
-    //                    issue W(g + 2) into stage g & 1 (one full step ahead, like r04's tap-ahead DMA).
-    // Patch buffers: a round of chunk c + 1 is written at a step's top into the buffer chunk c - 1 read; all of those reads (issued at a
-    // step's top) lie before that chunk's tap-8 hook.  Raw tile s + 1 is written at the top of raw step s into the buffer step s - 1 read.
-    // A staged unit loaded at the top of step g is converted at the top of step g + 2 (g + 1 for the late waves' last round): the hook of
-    // step g + 1 has drained it (a wave never loads at two consecutive steps), so the conversion's wait (vmcnt(3): the DMA just issued) is
-    // a dependency only, as in r04.
-    if constexpr (CG_MIDBAR) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // chunk 0's patch written, both weight stages landed
-        __builtin_amdgcn_s_barrier();
-        using Y3 = std::integral_constant<int, 3>;
-        auto chunk_mb = [&](auto modec, int c) {
-            constexpr int MODE = decltype(modec)::value;
-            static_for<0, 9>([&](auto tc) {
-                constexpr int T = decltype(tc)::value;
-                // ---- top of the step: staging of chunk c + 1 (MODE 0) / the raw tiles (MODE 2); no barrier ----
-                constexpr int EL = (MODE == 0 && T % 2 == 0 && T / 2 < NR) ? T / 2 : -1;                       // round the early waves load
-                constexpr int LL = (MODE == 0 && T % 2 == 1 && (T - 1) / 2 < NR) ? (T - 1) / 2 : -1;           // ... the late waves
-                if constexpr (MODE == 0) {
-                    constexpr int EC = (T % 2 == 0 && T >= 2 && T / 2 - 1 < NR) ? T / 2 - 1 : -1;              // round the early waves convert
-                    constexpr int LC = (T % 2 == 1 && T >= 3 && (T - 3) / 2 < NR) ? (T - 3) / 2 : ((T == 8 && NR == 4) ? 3 : -1);
-                    if (early) {
-                        if constexpr (EC >= 0) stage_write(std::integral_constant<int, EC < 0 ? 0 : EC>{}, Y3{}, c + 1, su);
-                        if constexpr (EL >= 0) stage_load(std::integral_constant<int, EL < 0 ? 0 : EL>{}, c + 1, su);
-                    } else {
-                        if constexpr (LC >= 0) stage_write(std::integral_constant<int, LC < 0 ? 0 : LC>{}, Y3{}, c + 1, su);
-                        if constexpr (LL >= 0) stage_load(std::integral_constant<int, LL < 0 ? 0 : LL>{}, c + 1, su);
-                    }
-                }
-                if constexpr (MODE == 2 && T == 0) raw_load(0, ru);
-                if constexpr (MODE == 2 && T == 1) raw_write(Y3{}, (c + 1) & 1, ru);            // tile 0 -> the buffer chunk c - 1 read
-                if constexpr (MODE == 2 && T == 6) { if (nraw > 1) raw_load(1, ru); }
-                mma_step(lds0 + (unsigned)((c & 1) * PBUF), false, (T / 3 - 1) * PW + (T % 3 - 1), (c + T) & 1, [&] {
-                    // my share of the NEXT step's weights has landed: only the loads issued at this step's top may stay in flight
-                    if constexpr (MODE == 0) {
-                        constexpr int E = EL >= 0 ? NL : 0, L = LL >= 0 ? NL : 0;
-                        if constexpr (E == L) wait_vmcnt<E>();
-                        else if (early) wait_vmcnt<E>();
-                        else wait_vmcnt<L>();
-                    } else if constexpr (MODE == 2 && T == 0) {
-                        wait_vmcnt<2 * RU>();
-                    } else if constexpr (MODE == 2 && T == 6) {
-                        if (nraw > 1) wait_vmcnt<2 * RU>(); else wait_vmcnt<0>();
-                    } else {
-                        wait_vmcnt<0>();
-                    }
-                    if constexpr (!(CG_ABLATE & 128)) __builtin_amdgcn_s_barrier();
-                    // refill the stage this step has finished reading with the weights of step + 2
-                    if constexpr (T + 2 <= 8) issue_w((int64_t)(T + 2) * C + c * 32, (c + T) & 1);
-                    else if constexpr (MODE == 0) issue_w((int64_t)(T + 2 - 9) * C + (c + 1) * 32, (c + T) & 1);
-                    else if constexpr (MODE == 2) { if (T + 2 - 9 < nraw) issue_w((int64_t)9 * C + (rb + T + 2 - 9) * 32, (c + T) & 1); }
-                }, no_after);
-            });
-        };
-        for (int c = cb; c + 1 < nc; ++c) chunk_mb(std::integral_constant<int, 0>{}, c);
-        if (HASRAW && nraw > 0) {
-            chunk_mb(std::integral_constant<int, 2>{}, nc - 1);
-            // raw tile s: weights in stage (nc + s) & 1, tile in patch buffer (nc + s) & 1
-            for (int s = 0; s < nraw; ++s) {
-                const bool nxt = s + 1 < nraw, nxt2 = s + 2 < nraw;
-                if (nxt) {
-                    raw_write(Y3{}, (nc + s + 1) & 1, ru);      // tile s + 1 -> the buffer step s - 1 read (loaded at the top of step s - 1 / tap 6)
-                    if (nxt2) raw_load(s + 2, ru);
-                }
-                mma_step(lds0 + (unsigned)(((nc + s) & 1) * PBUF), true, 0, (nc + s) & 1, [&] {
-                    if (nxt && nxt2) wait_vmcnt<2 * RU>(); else wait_vmcnt<0>();
-                    __builtin_amdgcn_s_barrier();
-                    if (nxt2) issue_w((int64_t)9 * C + (rb + s + 2) * 32, (nc + s) & 1);
-                }, no_after);
-            }
-        } else {
-            chunk_mb(std::integral_constant<int, 1>{}, nc - 1);
-        }
-    } else {
-    if constexpr (CG_PINGPONG) {
-        static_assert(!CG_MIDBAR && CG_PP_K >= 0 && CG_PP_K < TN, "ping-pong: r04 loop form");
-        if (!early) {      // group Y starts half a step late: it sits out barrier A_0 (group X's first top)
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-    }
     for (int c = cb; c + 1 < nc; ++c) chunk(std::integral_constant<int, 0>{}, c);
     if (HASRAW && nraw > 0) {
         chunk(std::integral_constant<int, 2>{}, nc - 1);
@@ -678,28 +510,18 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_kernel(const FridoGemm d) {
                 raw_write(std::integral_constant<int, 3>{}, (nc + s + 1) & 1, ru);      // tile s + 1 -> the buffer step s - 1 read
                 if (s + 2 < nraw) raw_load(s + 2, ru);
             }
-            mma_step(lds0 + (unsigned)(((nc + s) & 1) * PBUF), true, 0, (nc + s) & 1, no_hook, no_after);
+            mma_step(lds0 + (unsigned)(((nc + s) & 1) * PBUF), true, 0, (nc + s) & 1);
         }
     } else {
         chunk(std::integral_constant<int, 1>{}, nc - 1);
     }
-    if constexpr (CG_PINGPONG) {
-        if (early) __builtin_amdgcn_s_barrier();      // barrier A_n: the mid-step barrier of group Y's last step
-    }
-    }      // (!CG_MIDBAR)
     wait_vmcnt<0>();
 #if CG_PROF
     const unsigned cgp_loop1 = CGP_NOW();
     cgp[4] = cgp_loop1 - cgp_loop0;
 #endif
     status_raise(sat);
-    if constexpr (CG_ABLATE & 32) {       // (timing only) no epilogue: keep the accumulators live, store nothing
-        float sink = 0.f;
-        for (auto& ai : acc) for (auto& aj : ai) sink += aj[0] + aj[1] + aj[2] + aj[3];
-        if (sink == 1.2345e-30f) d.out_f32[0] = sink;
-        return;
-    }
-    tile_epilogue<BM, BN, 2, WM, false>(d, acc, smem, m0, n0, CG_PINGPONG ? wm * 2 + wn : wave, lane, 0, 0, kz);      // (the epilogue's wave id = 2 wm + wn)
+    tile_epilogue<BM, BN, 2, WM, false>(d, acc, smem, m0, n0, wave, lane, 0, 0, kz);
 #if CG_PROF
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the stores have left the wave (not: reached memory)
     cgp[6] = CGP_NOW() - cgp_loop1;

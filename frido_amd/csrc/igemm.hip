@@ -30,32 +30,19 @@ int frido_launch_convgn(const FridoGemm& d, int bm, hipStream_t s);
 int frido_launch_convgn_tiny(const FridoGemm& d, hipStream_t s);      // tile 40
 int frido_convgn_init();
 
-// Timing ablations of the bf16x3 main loop (tools/build_ablate.sh builds SEPARATE libraries with -DFRIDO_ABLATE=<mask>; the shipped
-// library is built with 0 and contains none of this): 1 = no DMA refills inside the loop, 2 = no fragment reads, 4 = no barriers /
-// vmcnt waits, 8 = no MFMAs.  Results are garbage; only the launch time means anything.
-// 1024 (r05, results stay CORRECT): stagger experiment of DESIGN.md section 7 item 5 -- on the two-per-CU (4-wave) tiles the workgroups
-// with dispatch ids 256 .. 511 (the second resident slot of the first round, if the dispatcher fills one slot per CU first) start
-// FRIDO_STAGGER_US microseconds late, so that from then on one slot's prologue / epilogue runs under the other slot's k-loop.
-#ifndef FRIDO_ABLATE
-#define FRIDO_ABLATE 0
-#endif
-#ifndef FRIDO_STAGGER_US
-#define FRIDO_STAGGER_US 8
-#endif
-// Run-time form of the same (for round 6; -DFRIDO_STAGGER_RT=1 builds only, the shipped library is built with 0 and is bit-identical to
-// the one without this code): the delay in QUARTER microseconds comes from FridoGemm.flags bits 8..15 (0 = none), the smallest grid it
-// applies to from bits 16..23 in units of 64 workgroups (0 = 768 workgroups), which workgroups wait from bits 24..25.
+// Start stagger (r05 experiment, shipped since r06; results unchanged): on the two-per-CU (4-wave) tiles the
+// workgroups with dispatch ids 256 .. 511 (the second resident slot of the first round, if the dispatcher fills one slot per CU first)
+// start late, so that from then on one slot's prologue / epilogue runs under the other slot's k-loop.  The delay in QUARTER microseconds
+// comes from FridoGemm.flags bits 8..15 (0 = none), the smallest grid it applies to from bits 16..23 in units of 64 workgroups
+// (0 = 768 workgroups), which workgroups wait from bits 24..25.
 // Python: FRIDO_STAGGER_US (a float) / FRIDO_STAGGER_MIN_WG / FRIDO_STAGGER_MODE (engine.py).
-// (FRIDO_STAGGER_RT itself: igemm_shared.h, next to the one-workgroup-per-CU form of the experiment)
+// (The one-workgroup-per-CU form of the same: igemm_shared.h stagger_one_per_cu)
 // (r06) -DIG_PROF=1 (tools/igemm_prof.py; never in the shipped build): every wave of the two-plane virtual-step loop sums the shader cycles
 // (s_memtime) it spends, per k-tile,  [0] waiting for the next stage's DMA in front of the barrier, [1] inside the barrier, [2] in the rest of
 // its three virtual steps (MFMAs, fragment reads and their lgkmcnt waits, DMA issue);  [3] = the whole loop, [4] = kernel start -> loop,
 // [5] = epilogue, [6] = k-tiles.  Stamps sit where lgkmcnt is 0 anyway.  convgn.hip has the same for the fused kernel (CG_PROF).
 #ifndef IG_PROF
 #define IG_PROF 0
-#endif
-#ifndef FRIDO_X3_PIPE_ALL
-#define FRIDO_X3_PIPE_ALL 0      // 1: also run the six-n-tile bf16x3 tiles (128 x 192, 64 x 192) on the virtual-k-step loop
 #endif
 
 namespace {
@@ -179,15 +166,15 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
         }
     }
     const int m0 = tm * BM, n0 = tn * BN;
-    if constexpr (((FRIDO_ABLATE & 1024) || FRIDO_STAGGER_RT) && NW == 4) {
+    if constexpr (NW == 4) {
         const int id = ((int)blockIdx.y * (int)gridDim.z + (int)blockIdx.z) * (int)gridDim.x + (int)blockIdx.x;
-        // run-time form: delay in QUARTER microseconds (a k-step of these tiles is ~1 us: sub-k-step offsets are the interesting ones for
+        // delay in QUARTER microseconds (a k-step of these tiles is ~1 us: sub-k-step offsets are the interesting ones for
         // one-round launches), smallest grid in units of 64 workgroups, and which workgroups wait: mode 0 = dispatch ids 256..511 (the
         // second slot of every CU if the dispatcher deals one workgroup per CU first), mode 1 = every other workgroup of an XCD among
         // the first 512 (the control: right only if the dispatcher fills a CU's two slots back to back)
-        const int ticks = FRIDO_STAGGER_RT ? ((d.flags >> 8) & 255) * 25 : FRIDO_STAGGER_US * 100;          // 100 MHz
-        const int min_wg = (FRIDO_STAGGER_RT && ((d.flags >> 16) & 255)) ? ((d.flags >> 16) & 255) * 64 : 768;
-        const int mode = FRIDO_STAGGER_RT ? (d.flags >> 24) & 3 : 0;
+        const int ticks = ((d.flags >> 8) & 255) * 25;          // 100 MHz
+        const int min_wg = ((d.flags >> 16) & 255) ? ((d.flags >> 16) & 255) * 64 : 768;
+        const int mode = (d.flags >> 24) & 3;
         const bool late = mode == 0 ? (id >= 256 && id < 512) : (id < 512 && ((id >> 3) & 1));
         if (ticks && late && (int)(gridDim.x * gridDim.y * gridDim.z) >= min_wg) {
             const uint64_t t0 = wall_clock64();
@@ -207,11 +194,8 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
     // ---- LDS-DMA assignments: wave w moves chunks w, w+4, ... ; lane l of a chunk lands at row l>>2, physical
     //      slot l&3, i.e. it must FETCH logical slot (l&3) ^ swz(row) ----
     // BK = 32: 64-B rows, 4 slots, slot q of row r at q ^ ((4 - (r>>2)) & 3);  BK = 64: 128-B rows, 8 slots, q ^ ((r>>1) & 7)
-    // (ablation 64, dense bf16x3 timing only: a piece = 8 rows x 128 contiguous bytes of a plane-interleaved operand; the "lo" piece
-    //  covers the chunk's rows 8..15 -- same instruction count and bytes as the shipped 16 rows x 64 B pieces, full 128-B lines)
-    constexpr bool AB64 = (FRIDO_ABLATE & 64) && NS == 2 && !CONV;
-    const int lrow = (BK == 32 && !AB64) ? lane >> 2 : lane >> 3;
-    const int lq = AB64 ? (lane & 7) : BK == 32 ? (lane & 3) ^ ((4 - ((lrow >> 2) & 3)) & 3)
+    const int lrow = BK == 32 ? lane >> 2 : lane >> 3;
+    const int lq = BK == 32 ? (lane & 3) ^ ((4 - ((lrow >> 2) & 3)) & 3)
                             : (lane & 7) ^ ((((wave & 1) << 2) + (lrow >> 1)) & 7);
     // conv: element offset of tap (0,0) of this row's receptive field + a bit mask of the taps that fall inside
     // the (logical) input; with resampling folded in (up/dn shifts) the per-tap offsets are tabulated instead
@@ -242,7 +226,7 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
             a_off[j] = ((int64_t)(b * d.Hs + oy * d.stride - pady) * d.Ws + (ox * d.stride - padx)) * d.Cin + lq * 8;
         } else {
             m = m < d.M ? m : d.M - 1;      // rows past M are clamped (their outputs are masked)
-            a_off[j] = (int64_t)m * d.lda * ((FRIDO_ABLATE & 16) ? 2 : 1) + lq * 8;
+            a_off[j] = (int64_t)m * d.lda + lq * 8;
         }
     }
     const frido_bf16* __restrict__ A2b = d.A2;
@@ -250,13 +234,11 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
     int64_t b_off[JB];
 #pragma unroll
     for (int j = 0; j < JB; ++j) {
-        constexpr bool BIL = (FRIDO_ABLATE & 512) && NS == 2;      // timing only: 8 rows x 128 B weight pieces
-        int row = (wave + NW * j) * CHR + (BIL ? lane >> 3 : lrow);
+        int row = (wave + NW * j) * CHR + lrow;
         row = row < BN ? row : BN - 1;                            // (uneven dealing: this wave has no chunk j; never issued)
         int n = n0 + (d.geglu ? row : chan_of_pos(row));      // LDS row `row` holds channel chan_of_pos(row): see tile_epilogue
         n = n < d.N ? n : d.N - 1;
-        if (BIL) n = n < d.N - 8 ? n : d.N - 9;      // (the "lo" piece reads 8 rows further down: stay inside the buffer)
-        b_off[j] = BIL ? (int64_t)n * d.ldb * 2 + (lane & 7) * 8 : (int64_t)n * d.ldb * ((FRIDO_ABLATE & 16) && !CONV ? 2 : 1) + lq * 8;
+        b_off[j] = (int64_t)n * d.ldb + lq * 8;
     }
 
     // k-tile range of this workgroup (split-K: gridDim.z slices)
@@ -270,9 +252,7 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
     // keep the zero page's address in SGPRs (otherwise hipcc re-loads it from the GOT inside the k-loop)
     unsigned long long zero_addr = (unsigned long long)reinterpret_cast<const void*>(g_zero_page);
     asm volatile("" : "+s"(zero_addr));
-    const int64_t b_lo = ((FRIDO_ABLATE & 512) && NS == 2) ? (int64_t)16 * d.ldb : AB64 ? (int64_t)16 * d.ldb : (FRIDO_ABLATE & 16) && !CONV ? 32 : d.b_lo;
-    constexpr int KADV = (FRIDO_ABLATE & 16) && !CONV ? 2 * BK : BK;      // elements a dense source pointer advances per k-tile
-    constexpr int KADVB = ((FRIDO_ABLATE & 512) && NS == 2) ? 2 * BK : KADV;
+    const int64_t b_lo = d.b_lo;
 
     // ---- incremental source pointers.  Inside one SEGMENT of the k-walk (the channel chunks of one conv tap, the whole K of
     //      a dense operand, the appended A2 range) every piece just advances by BK elements per k-tile; the per-piece
@@ -282,7 +262,7 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
     int astep[JA];                      // BK, or 0 for a piece parked on the zero page
     const frido_bf16* bptr[JB];
 #pragma unroll
-    for (int j = 0; j < JB; ++j) bptr[j] = Bb + b_off[j] + (int64_t)kt0 * KADVB;
+    for (int j = 0; j < JB; ++j) bptr[j] = Bb + b_off[j] + (int64_t)kt0 * BK;
     int ktn = kt0;                      // next k-tile to issue
     int seg_left = 0;                   // k-tiles left in the current segment
     int64_t alo_cur = d.a_lo;           // hi -> lo plane distance of the operand the segment reads
@@ -336,10 +316,9 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
         } else {
 #pragma unroll
             for (int j = 0; j < JA; ++j) {
-                aptr[j] = Ab + a_off[j] + (int64_t)ktn * KADV;
-                astep[j] = KADV;
+                aptr[j] = Ab + a_off[j] + (int64_t)ktn * BK;
+                astep[j] = BK;
             }
-            if constexpr ((FRIDO_ABLATE & 16) && !CONV) alo_cur = AB64 ? (int64_t)16 * d.lda : 32;
             seg_left = nk1 - ktn;
         }
     };
@@ -379,7 +358,7 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
                 if (NS == 2)
                     __builtin_amdgcn_global_load_lds((gptr_t)(bptr[j] + b_lo), (lptr_t)(sb + PLANE + BM * ROWB + j * (NW * 1024)), 16, 0, 0);
             }
-            bptr[j] += KADVB;
+            bptr[j] += BK;
         }
         advance();
     };
@@ -495,7 +474,7 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
         } else if (st + 1 == nsteps) {
             step(std::integral_constant<int, 0>{}, F_{}, st / KS, st % KS);
         }
-    } else if constexpr (NS == 2 && (BN / 2 / 16 <= 4 || W8 || FRIDO_X3_PIPE_ALL)) {
+    } else if constexpr (NS == 2 && (BN / 2 / 16 <= 4 || W8)) {
         // ---- bf16x3 main loop: software-pipelined over VIRTUAL k-steps (r03).  A stage holds the hi and lo planes of one 32-deep
         //      k-tile (= the LDS bytes of one BK = 64 bf16 stage); its product hi*hi + hi*lo + lo*hi is walked as three virtual
         //      k-steps, each TM x TN MFMAs on ONE pixel-fragment set and ONE weight-fragment set:
@@ -554,12 +533,10 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
             unsigned char* sb = ring + dbuf * STAGE + pl * PLANE + wave * 1024;
             if constexpr (idx < JA) {
                 const frido_bf16* src = (pl && astep[idx]) ? aptr[idx] + alo_cur : aptr[idx];
-                if constexpr (FRIDO_ABLATE & 32) src = reinterpret_cast<const frido_bf16*>(zero_addr) + (lane & 3) * 8;   // same 64 bytes for every piece
                 __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sb + idx * (NW * 1024)), 16, 0, 0);
             } else {
                 constexpr int j = idx - JA;
                 const frido_bf16* srcb = bptr[j] + (pl ? b_lo : 0);
-                if constexpr (FRIDO_ABLATE & 32) srcb = reinterpret_cast<const frido_bf16*>(zero_addr) + (lane & 3) * 8;
                 if (JBR == 0 || j < JB - 1 || wave < JBR)
                     __builtin_amdgcn_global_load_lds((gptr_t)srcb, (lptr_t)(sb + BM * ROWB + j * (NW * 1024)), 16, 0, 0);
             }
@@ -568,11 +545,9 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
 #pragma unroll
             for (int j = 0; j < JA; ++j) aptr[j] += astep[j];
 #pragma unroll
-            for (int j = 0; j < JB; ++j) bptr[j] += KADVB;
+            for (int j = 0; j < JB; ++j) bptr[j] += BK;
             issue_end();
         };
-        // (ablation 256: waves 4..7 of an 8-wave workgroup take the refill's pieces half a window later than waves 0..3)
-        const bool late = (FRIDO_ABLATE & 256) && NW == 8 && wave >= 4;
         auto vstep = [&](auto vc, auto qc, auto prec, int kt) {
             constexpr int V = decltype(vc)::value, Q = decltype(qc)::value;
             constexpr bool PRE = decltype(prec)::value;             // v2 only: a next stage exists
@@ -582,24 +557,22 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
             if constexpr (V == 2) {
                 if constexpr (PRE) {
                     // stage kt + 1 must have landed; past this barrier every wave holds stage kt in registers: its slot is free
-                    if constexpr (!(FRIDO_ABLATE & 4)) {
 #if IG_PROF
-                        igp_a = IGP_NOW(); igp[2] += igp_a - igp_prev;
+                    igp_a = IGP_NOW(); igp[2] += igp_a - igp_prev;
 #endif
-                        if (kt + D - 1 < nk) wait_stages(std::integral_constant<int, D - 2>{});
-                        else wait_younger(nk - kt - 2);
+                    if (kt + D - 1 < nk) wait_stages(std::integral_constant<int, D - 2>{});
+                    else wait_younger(nk - kt - 2);
 #if IG_PROF
-                        igp_prev = IGP_NOW(); igp[0] += igp_prev - igp_a; igp_a = igp_prev;
+                    igp_prev = IGP_NOW(); igp[0] += igp_prev - igp_a; igp_a = igp_prev;
 #endif
-                        __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_s_barrier();
 #if IG_PROF
-                        igp_prev = IGP_NOW(); igp[1] += igp_prev - igp_a; igp[6] += 1;
+                    igp_prev = IGP_NOW(); igp[1] += igp_prev - igp_a; igp[6] += 1;
 #endif
-                    }
                     nbuf = buf + 1 == D ? 0 : buf + 1;
                     ra = afr + nbuf * STAGE;
                     rb = bfr + nbuf * STAGE;
-                    dma = kt + D < nk && !(FRIDO_ABLATE & 1);
+                    dma = kt + D < nk;
                     dbuf = buf;
                     if (dma) issue_begin();
                 } else {
@@ -612,11 +585,7 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
             constexpr int RG = TN > 2 ? TN - 2 : 1;
             static_for<0, TN>([&](auto jc) {
                 constexpr int j = decltype(jc)::value;
-#ifdef IG_FAIRPRIO
-                // (A/B, r06) least progress first within a k-tile: priority 3 .. 0 over its 3 TN MFMA groups (8-wave tiles: two waves per SIMD)
-                if constexpr (NW == 8) __builtin_amdgcn_s_setprio(3 - ((V == 2 ? 0 : (V == 0 ? 1 : 2)) * TN + j) * 4 / (3 * TN));
-#endif
-                if constexpr (!(FRIDO_ABLATE & 2) && j < RG) static_for<j * NR / RG, (j + 1) * NR / RG>([&](auto rc) {
+                if constexpr (j < RG) static_for<j * NR / RG, (j + 1) * NR / RG>([&](auto rc) {
                     constexpr int r = decltype(rc)::value;
                     if constexpr (V == 0) fb[1 - Q][r] = lds_read128(rb + r * 16 * ROWB);
                     else if constexpr (V == 1) fa[1][r] = lds_read128(ra + r * 16 * ROWB);
@@ -624,22 +593,14 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
                     else fb[1 - Q][r - TM] = lds_read128(rb + (r - TM) * 16 * ROWB);
                 });
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (!(FRIDO_ABLATE & 8)) {
-                    if constexpr (FRIDO_ABLATE & 128) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-                    for (int i = 0; i < TM; ++i)
-                        acc[i][j] = mfma_op<NS>(fb[BS][j], fa[AS][i], acc[i][j]);   // weights first: C^T tiles
-                    if constexpr (FRIDO_ABLATE & 128) __builtin_amdgcn_s_setprio(0);
-                } else {
-                    asm volatile("" :: "v"(fb[BS][j]), "v"(fa[AS][0]), "v"(fa[AS][TM - 1]));      // keep the fragment reads alive
-                }
+                for (int i = 0; i < TM; ++i)
+                    acc[i][j] = mfma_op<NS>(fb[BS][j], fa[AS][i], acc[i][j]);   // weights first: C^T tiles
                 __builtin_amdgcn_sched_barrier(0);
                 constexpr int g = V == 2 ? j : (V == 0 ? TN + j : 2 * TN + j);          // group index within the refill begun at v2
                 if constexpr (g < NG) {
                     if (dma) {
-                        constexpr int g2 = (g + NG / 2) % NG;
-                        if (!late) static_for<g * NPC / NG, (g + 1) * NPC / NG>([&](auto pc) { piece(pc); });
-                        else static_for<g2 * NPC / NG, (g2 + 1) * NPC / NG>([&](auto pc) { piece(pc); });
+                        static_for<g * NPC / NG, (g + 1) * NPC / NG>([&](auto pc) { piece(pc); });
                         if constexpr (g == NG - 1) refill_end();
                     }
                 }
@@ -654,11 +615,6 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
         using I1 = std::integral_constant<int, 1>;
         using I2 = std::integral_constant<int, 2>;
         int kt = 0;
-#ifdef IG_PRIO
-        // (A/B, r06) static priority for the second-dispatched half of an 8-wave workgroup: tools/igemm_prof.py shows it losing the MFMA
-        // arbitration on every k-tile (2120 against 1620 cycles) while the older half waits for it at the barrier
-        if (NW == 8 && wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
 #if IG_PROF
         igp_prev = IGP_NOW(); igp[4] = igp_prev - igp_t0; igp_loop0 = igp_prev;
 #endif
@@ -678,24 +634,13 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
     } else {
     // ---- plain loop (bf16 BK = 32 tiles; bf16x3 tiles with six n-tiles per wave, whose second fragment sets would spill: those run
     //      as TWO 4-wave workgroups per CU on a 2-slot ring, the other workgroup's MFMAs covering this one's read phase) ----
-    // (r06) MID-STEP BARRIER form of the two-slot two-plane tiles (128 x 192, 64 x 192, 256 x 192; convgn.hip has the long version): k-tile kt's
-    // barrier sits at the head of its LAST weight slab -- every fragment of the tile is in registers, TM MFMA triples are ready right after
-    // the release -- instead of at its top, where the release is followed by the DMA issue and an LDS round trip with the matrix pipe idle.
-    // Hook of k-tile kt: my share of tile kt + 1 has landed (vmcnt(0): it is all that is in flight), barrier (tile kt + 1 published, slot
-    // kt & 1 free), issue tile kt + 2 into slot kt & 1.  Same MFMAs, same operands, same order: bit-identical results.
-    constexpr bool MIDBAR = FRIDO_MIDBAR != 0 && NS == 2 && D == 2 && KG == 1 && TN > 1 && BK == 32;
-    // ---- prologue: fill D-1 stages (mid-step form: both slots) ----
+    // ---- prologue: fill D-1 stages ----
 #pragma unroll
-    for (int s = 0; s < D - 1 + (MIDBAR ? 1 : 0); ++s)
+    for (int s = 0; s < D - 1; ++s)
         if (s < nk) issue(s);
-    if constexpr (MIDBAR) {
-        wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-    }
 
     int buf = 0;
     for (int kt = 0; kt < nk; ++kt) {
-        if constexpr (!MIDBAR) {
         // tile kt must have landed: at most the loads of the (D-2) younger tiles may stay in flight
         if (kt + D - 2 < nk) wait_vmcnt<(D - 2) * G::LPT>();
         else wait_tail<D - 3, G::LPT>(nk - 1 - kt);
@@ -704,7 +649,6 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
             int nb_ = buf + D - 1;
             nb_ = nb_ >= D ? nb_ - D : nb_;
             issue(nb_);
-        }
         }
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -730,16 +674,17 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
                     if (j > 0) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(NS) : "memory");
                 } else {
                     if (j > 0 || TN == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    if constexpr (MIDBAR) {
-                        wait_vmcnt<0>();
-                        __builtin_amdgcn_s_barrier();
-                        if (kt + 2 < nk) issue(buf);
-                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (FRIDO_SLAB0 != 0 && NS == 2 && TN > 1 && (TM & 1) == 0) {
-                    if (j == 0) {      // (r06) pixel slabs in groups of GI, pass-major inside a group (igemm_shared.h FRIDO_SLAB0)
-                        constexpr int GI = FRIDO_SLAB0 == 2 ? TM : 2;
+                if constexpr (NS == 2 && TN > 1 && (TM & 1) == 0) {
+                    // (r06) first weight slab of a two-plane k-step: the MFMAs of pixel slab i used to issue as soon as ITS fragments were
+                    // back -- three MFMAs on ONE accumulator in a row (hi*lo, lo*hi, hi*hi), the first separated from the second by the
+                    // s_waitcnt of the lo plane: a dependent MFMA chain with an issue slot in it (MI355X_MICROARCH.md constants table: +43
+                    // cycles for the first extra state between two MFMAs on the same accumulator; a plain dependent pair waits for the pass
+                    // pipeline too).  Slabs are issued in PAIRS, pass-major (acc[i] and acc[i + 1] alternate: every dependent MFMA has an
+                    // independent one in front of it).  The per-accumulator order of the three products is unchanged: bit-identical results.
+                    if (j == 0) {
+                        constexpr int GI = 2;
                         static_for<0, TM / GI>([&](auto gc) {
                             constexpr int i0 = decltype(gc)::value * GI;
                             asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(NS * (TM - GI - i0) + NS) : "memory");

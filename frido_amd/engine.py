@@ -15,7 +15,7 @@ import contextlib
 import os
 SIDE_STREAM = os.environ.get("FRIDO_SIDE_STREAM", "0") != "0"   # independent projections of an attention block on a side stream: measured -2.9 % (the fork / join nodes cost more than the overlap buys), off by default
 GEMM_FLAGS = int(os.environ.get("FRIDO_GEMM_FLAGS", "0"))     # FridoGemm.flags A/B switches (include/frido_hip.h)
-# Staggered start (r05 experiment, SHIPPED in r06: the library is built with -DFRIDO_STAGGER_RT=1; results are
+# Staggered start (r05 experiment, SHIPPED in r06: the kernels always honour FridoGemm.flags bits 8..25; results are
 # unchanged bit for bit): start delay in microseconds of the second resident slot (dispatch ids 256 .. 511) of a multi-round two-per-CU
 # GEMM launch (>= 768 workgroups unless FRIDO_STAGGER_MIN_WG says otherwise), so that one slot's prologue / epilogue runs under the
 # other's k-loop from then on.  12 us: + 2.1 % end to end (interleaved, profiles/r06_stagger_*.txt; 8 us on the r05 boxes: + 2.0 ... 2.5 %).

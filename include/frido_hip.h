@@ -137,7 +137,7 @@ typedef struct FridoGemm {
                                    epilogue, bit 1 = do not hoist a launch-wide timestep vector into the bias, bit 4 = do not take the
                                    streamlined epilogues (bit 5 / 6: only the split-K / GEGLU one); TIMING EXPERIMENTS ONLY
                                    (results are garbage): bit 2 = skip the whole epilogue, bit 3 = skip only its stores;
-                                   bits 8..15 / 16..23 / 24..25 (r05 experiment, honoured only by -DFRIDO_STAGGER_RT=1 builds of igemm.hip,
+                                   bits 8..15 / 16..23 / 24..25 (staggered start of igemm.hip: r05 experiment, shipped since r06,
                                    results unchanged): start delay in quarter microseconds of the workgroups with dispatch ids 256..511 of a
                                    two-per-CU tile / smallest grid it applies to in units of 64 workgroups (0 = 768) / which workgroups wait; bit 26: the
                                    one-workgroup-per-CU kernels too (odd XCDs of the first 256 workgroups wait);

@@ -52,8 +52,9 @@ def test_abi_library_loads_and_exports_every_declared_symbol():
 
 def test_shipped_libraries_are_not_profiling_or_experiment_builds():
     """r06: -DCG_PROF / -DIG_PROF builds (tools/cg_prof.py, tools/igemm_prof.py) export a reader for their per-wave cycle sums and carry an
-    s_memtime + lgkmcnt(0) in every k-step; the loop-form experiments (CG_MIDBAR, CG_PINGPONG, FRIDO_MIDBAR) are off in what ships.  Both
-    libraries in the tree must be the plain build: no profiling entry point, and the macros' defaults in the sources say 0."""
+    s_memtime + lgkmcnt(0) in every k-step.  Both libraries in the tree must be the plain build: no profiling entry point, and the two
+    macros' defaults in the sources say 0.  The build-time variants that were measured and rejected (loop forms, timing ablations, priority
+    A/Bs, the division form of SiLU, the compile-time stagger switch) are retired: their names occur nowhere in the kernel sources or the header."""
     import os
     import re
     for key in ("f16", "bf16"):
@@ -62,10 +63,19 @@ def test_shipped_libraries_are_not_profiling_or_experiment_builds():
             assert not hasattr(L, name), f"{_lib.LIB_PATHS[key]} is a profiling build ({name})"
     src = os.path.join(os.path.dirname(_lib.__file__), "csrc")
     text = open(os.path.join(src, "convgn.hip")).read() + open(os.path.join(src, "igemm.hip")).read() + open(os.path.join(src, "igemm_shared.h")).read()
-    for macro in ("CG_PROF", "IG_PROF", "CG_MIDBAR", "CG_PINGPONG", "FRIDO_MIDBAR", "CG_ABLATE", "FRIDO_ABLATE"):
+    for macro in ("CG_PROF", "IG_PROF"):
         m = re.search(r"#ifndef %s\n#define %s (\d+)" % (macro, macro), text)
         assert m and m.group(1) == "0", macro
-    assert re.search(r"#ifndef FRIDO_SILU_DIV\n#define FRIDO_SILU_DIV 0", open(os.path.join(src, "common.h")).read())
+    retired = ("CG_MIDBAR", "CG_PINGPONG", "CG_PP_K", "FRIDO_MIDBAR", "CG_ABLATE", "FRIDO_ABLATE", "FRIDO_SILU_DIV", "FRIDO_SLAB0",
+               "FRIDO_X3_PIPE_ALL", "FRIDO_STAGGER_RT", "FLASH_DS_KDB", "FLASH_DS_COUNTED", "CG_PRIO", "CG_FAIRPRIO", "IG_PRIO", "IG_FAIRPRIO")
+    files = [os.path.join(os.path.dirname(os.path.dirname(_lib.__file__)), "include", "frido_hip.h")]
+    for root, _, names in os.walk(src):
+        files += [os.path.join(root, n) for n in names]
+    assert len(files) >= 12      # the header, eight .hip files, two shared headers, the Makefile
+    for path in files:
+        body = open(path, "rb").read()
+        for name in retired:
+            assert name.encode() not in body, f"{path} still names the retired build-time variant {name}"
 
 
 def test_bad_descriptors_are_rejected_without_touching_a_device():

@@ -1,9 +1,10 @@
 #!/bin/bash
 # Variant builds of the library for interleaved A/B runs (tools/ab.sh lib ...): igemm.hip + convgn.hip compiled under extra flags, linked
 # with the default build's other objects (run `make -C frido_amd/csrc` first).   tools/build_variants.sh name "flags" [name "flags" ...]
+#   e.g. the profiling builds of tools/cg_prof.py / tools/igemm_prof.py:  tools/build_variants.sh prof "-DCG_PROF=1" igprof "-DIG_PROF=1"
 #   name = head : the two sources and igemm_shared.h as committed at HEAD (the baseline of an uncommitted kernel change)
 cd "$(dirname "$0")/.." && mkdir -p tools/ablate
-FL="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Iinclude -Wno-unused-result -ffp-contract=on -DFRIDO_STAGGER_RT=1"
+FL="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Iinclude -Wno-unused-result -ffp-contract=on"
 while [ $# -ge 2 ]; do
   name=$1; flags=$2; shift 2
   (

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where do the waves of the fused GroupNorm + conv kernel spend their cycles?  Runs ONE fused launch on a library built with -DCG_PROF=1
--DCG_MIDBAR=0 (tools/build_variants.sh prof "-DCG_PROF=1 -DCG_MIDBAR=0") and prints the per-wave cycle sums the kernel leaves behind
+(tools/build_variants.sh prof "-DCG_PROF=1") and prints the per-wave cycle sums the kernel leaves behind
 (convgn.hip CG_PROF).   FRIDO_LIB=$PWD/tools/ablate/libfrido_prof.so python tools/cg_prof.py B H W C Cout spade(0/1) skipC [tile]"""
 import ctypes as C
 import os

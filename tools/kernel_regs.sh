@@ -1,5 +1,6 @@
 #!/bin/bash
 # compact register / scratch report for one HIP source of the library: tools/kernel_regs.sh frido_amd/csrc/igemm.hip [filter]
+# (compiled with the CXXFLAGS of frido_amd/csrc/Makefile: the report is of the shipped build)
 src=$1; filt=${2:-.}
 cd "$(dirname "$src")"
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -I. -Wno-unused-result -ffp-contract=on \

@@ -75,8 +75,8 @@ def score(times, members, progs):
 
 def tune(progs, time_forward, sig_of, kind_gemm, *, min_gain=0.015, min_share=0.002, stagger=(), min_wg=512, log=print):
     """Coordinate descent over signatures, heaviest first.  time_forward() -> times[pi][rep][oi] in ms; raises on a rejected descriptor.
-    stagger: start delays (quarter microseconds) to try on the 4-wave-tile launches of at least min_wg workgroups (needs a
-    -DFRIDO_STAGGER_RT=1 library with FRIDO_STAGGER_MIN_WG <= min_wg in the environment).
+    stagger: start delays (quarter microseconds) to try on the 4-wave-tile launches of at least min_wg workgroups (needs
+    FRIDO_STAGGER_MIN_WG <= min_wg in the environment).
     Returns [(signature, old tile, new tile, old score, new score, delay)] of the changes that were kept."""
     base = time_forward()
     total = sum(statistics.median(rep[oi] for rep in base[pi]) for pi in range(len(progs)) for oi in range(len(progs[pi].ops)))
@@ -111,7 +111,7 @@ def tune(progs, time_forward, sig_of, kind_gemm, *, min_gain=0.015, min_share=0.
             f"{cur * 1e3:.1f} us -> best {best_t} {best_s * 1e3:.1f} us  {'KEPT' if keep else 'unchanged'}")
         best_q = 0
         if stagger and st0.nsplit == 2 and st0.tile in TILE_DIMS and (workgroups(st0) or 0) >= min_wg:
-            # start delay of the second resident slot (FridoGemm.flags bits 8..15, -DFRIDO_STAGGER_RT=1 builds): the same in-context score
+            # start delay of the second resident slot (FridoGemm.flags bits 8..15): the same in-context score
             ref_s = best_s if keep else cur
             q_s = ref_s
             for q in stagger:
@@ -142,7 +142,7 @@ def main():
     ap.add_argument("--min-gain", type=float, default=0.015)
     ap.add_argument("--out", default="gpurun_out/tune_in_context.json")
     ap.add_argument("--stagger", default="", help="comma-separated start delays in microseconds to try per signature, e.g. 1,2,4,6,8,12,16 "
-                                                  "(FRIDO_LIB = a -DFRIDO_STAGGER_RT=1 build, FRIDO_STAGGER_MIN_WG=<--min-wg> in the environment)")
+                                                  "(FRIDO_STAGGER_MIN_WG=<--min-wg> in the environment)")
     ap.add_argument("--min-wg", type=int, default=512)
     ap.add_argument("--write-cache", default="", help="write a tile cache = the loaded one with the kept changes (same format as profiles/tune_cache.json)")
     a = ap.parse_args()
