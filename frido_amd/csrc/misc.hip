@@ -1,7 +1,7 @@
 // Small HBM-bound kernels of the sampling loop: operand packing, layout changes, the fused
 // vector-quantiser lookup, the DDIM/PLMS state update (with CFG mix, Adams-Bashforth combine and a
 // counter-based Philox RNG so results do not depend on how the batch is sharded over GPUs), the stage
-// hand-off block mean, and a few utility fills.
+// hand-off block mean, the ancestral (DDPM) state update, and a few utility fills.
 #include "common.h"
 
 namespace {
@@ -253,6 +253,69 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const FridoSamplerSte
     }
 }
 
+// ---- ancestral (DDPM) update: FridoSamplerStep.hist_mode == FRIDO_STEP_ANCESTRAL ----------------------
+// frido.py:1246-1258 (p_mean_variance: predict_start_from_noise / clamp / q_posterior with ch_start, ch_end) and :1286-1305 (p_sample),
+// expression for expression in fp32, on the whole NHWC state in ONE pass of 16-byte accesses: lane = 4 consecutive floats of
+// x[B][HW][Cx] (HW * Cx is a multiple of 4, so a group never straddles two samples).  Coefficient row: {sqrt_recip_ac, sqrt_recipm1_ac,
+// post_coef1, post_coef2, sigma = nonzero_mask * exp(0.5 * posterior_log_variance_clipped), clip}.  Channels outside [start, start + nch)
+// keep x0 = x and mean = x; the clamp covers EVERY channel (x_recon.clamp_ is in place on the whole tensor); noise is zeroed on channels
+// [0, start) only (frido.py:1293-1296 with the split head: at stage 0 nothing is zeroed).  Philox groups are numbered over the flat
+// sample (frido_randn's numbering with per_sample = HW * Cx), draw = step + coef_row_offset + 1.
+__global__ __launch_bounds__(256) void ancestral_step_kernel(const FridoSamplerStep d) {
+    const int64_t gps = ((int64_t)d.HW * d.Cx) >> 2;    // groups per sample
+    const int64_t groups = (int64_t)d.B * gps;
+    const int step = d.step ? *d.step : 0;
+    const float* cf = d.coef + (int64_t)(step + d.coef_row_offset) * COEF_ROW;
+    const float c_recip = cf[0], c_recipm1 = cf[1], coef1 = cf[2], coef2 = cf[3], sigma = cf[4];
+    const bool clip = cf[5] != 0.f;
+    const uint64_t seed = d.rng_dev ? (uint64_t)d.rng_dev[0] : d.seed;
+    const int64_t sample0 = d.rng_dev ? d.rng_dev[1] : d.sample0;
+    const int end = d.start + d.nch;
+    const bool tape_flat = d.noise && d.noise_c0 == 0;   // the tape has the state's own layout: one 16-byte load
+    bool bad = false;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+        const float4 xq = reinterpret_cast<const float4*>(d.x)[g];
+        const float xv[4] = {xq.x, xq.y, xq.z, xq.w};
+        const int64_t f0 = g * 4;
+        int64_t pix = f0 / d.Cx;
+        int c = (int)(f0 - pix * d.Cx);
+        float nz[4] = {0.f, 0.f, 0.f, 0.f};
+        if (sigma != 0.f && d.write_x) {
+            if (tape_flat) {
+                const float4 nq = reinterpret_cast<const float4*>(d.noise + (int64_t)step * d.noise_stride)[g];
+                nz[0] = nq.x; nz[1] = nq.y; nz[2] = nq.z; nz[3] = nq.w;
+            } else if (d.noise) {
+                int64_t pp = pix;
+                int cc = c;
+                for (int e = 0; e < 4; ++e) {
+                    if (cc >= d.noise_c0) nz[e] = d.noise[(int64_t)step * d.noise_stride + pp * d.noise_C + (cc - d.noise_c0)];
+                    if (++cc == d.Cx) { cc = 0; ++pp; }
+                }
+            } else {
+                const int64_t b = g / gps;
+                randn4(seed, sample0 + b, (uint32_t)(step + d.coef_row_offset) + 1u, (uint32_t)d.rng_stream, (uint32_t)(g - b * gps), nz);
+            }
+        }
+        float x0v[4], xo[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool active = c >= d.start && c < end;
+            float x0 = xv[e];
+            if (active) x0 = __fsub_rn(__fmul_rn(c_recip, xv[e]), __fmul_rn(c_recipm1, d.eps_cond[pix * d.nch + (c - d.start)]));
+            if (clip) x0 = x0 < -1.0f ? -1.0f : (x0 > 1.0f ? 1.0f : x0);      // (a NaN stays a NaN, like torch's clamp_)
+            const float mean = active ? __fadd_rn(__fmul_rn(coef1, x0), __fmul_rn(coef2, xv[e])) : xv[e];
+            const float nv = c < d.start ? 0.f : nz[e];
+            x0v[e] = x0;
+            xo[e] = __fadd_rn(mean, __fmul_rn(sigma, __fmul_rn(nv, d.temperature)));
+            bad |= !(fabsf(xo[e]) <= 3.0e38f);
+            if (++c == d.Cx) { c = 0; ++pix; }
+        }
+        if (d.pred_x0) reinterpret_cast<float4*>(d.pred_x0)[g] = make_float4(x0v[0], x0v[1], x0v[2], x0v[3]);
+        if (d.write_x) reinterpret_cast<float4*>(d.x_out)[g] = make_float4(xo[0], xo[1], xo[2], xo[3]);
+    }
+    status_raise(false, bad);
+}
+
 // ---- stage hand-off -------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void handoff_kernel(const FridoHandoff d) {
     const int bs = 1 << d.levels;
@@ -396,8 +459,20 @@ extern "C" int frido_vq(const FridoVq* d, frido_stream_t s) {
 
 extern "C" int frido_sampler_step(const FridoSamplerStep* d, frido_stream_t s) {
     FRIDO_REQUIRE(d && d->x && d->eps_cond && d->coef, "null pointer");
-    FRIDO_REQUIRE(d->nch > 0 && d->nch <= 12 && d->start >= 0 && d->start + d->nch <= d->Cx, "bad channel range");
+    FRIDO_REQUIRE(d->nch > 0 && d->start >= 0 && d->start + d->nch <= d->Cx, "bad channel range");
     FRIDO_REQUIRE(!d->write_x || d->x_out, "x_out missing");
+    if (d->hist_mode == FRIDO_STEP_ANCESTRAL) {
+        FRIDO_REQUIRE(!d->hist_ring && !d->eps_uncond && !d->hist1 && !d->hist2 && !d->hist3 && !d->eps_out,
+                      "ancestral step: takes one eps and no history (no eps_uncond / eps_out / hist1..3 / hist_ring)");
+        FRIDO_REQUIRE(d->B > 0 && d->HW > 0 && (((int64_t)d->HW * d->Cx) & 3) == 0, "ancestral step: HW * Cx must be a multiple of 4");
+        FRIDO_REQUIRE((((uintptr_t)d->x | (uintptr_t)d->x_out | (uintptr_t)d->pred_x0 | (uintptr_t)d->noise) & 15) == 0 && (d->noise_stride & 3) == 0,
+                      "ancestral step: 16-byte aligned state, outputs and noise tape");
+        FRIDO_REQUIRE(!d->noise || (d->noise_c0 >= 0 && d->noise_c0 <= d->start && d->noise_C == d->Cx - d->noise_c0),
+                      "ancestral step: the noise tape spans channels [noise_c0, Cx) with noise_c0 <= start");
+        hipLaunchKernelGGL(ancestral_step_kernel, dim3(grid_for(((int64_t)d->B * d->HW * d->Cx) >> 2, 2048)), dim3(256), 0, (hipStream_t)s, *d);
+        return frido_check_launch("sampler_step (ancestral)");
+    }
+    FRIDO_REQUIRE(d->nch <= 12, "bad channel range");
     FRIDO_REQUIRE(!d->hist2 || d->hist1, "history must be contiguous");
     FRIDO_REQUIRE(!d->hist_mode || (d->hist_ring && d->step && d->hist_stride >= (int64_t)d->B * d->HW * d->nch &&
                                     (d->hist_mode == 1 || d->hist_mode == 3) && !d->hist1 && !d->eps_out),

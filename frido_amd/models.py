@@ -585,15 +585,16 @@ class FridoDiffusion(_Base):
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys)
 
-    # -- schedule buffers (frido.py:127-155) --
+    # -- schedule buffers (frido.py:127-168) --
     def register_schedule(self, given_betas=None, beta_schedule="linear", timesteps=1000, linear_start=1e-4,
                           linear_end=2e-2, cosine_s=8e-3):
         betas = given_betas if given_betas is not None else schedules.make_beta_schedule(
             beta_schedule, timesteps, linear_start=linear_start, linear_end=linear_end, cosine_s=cosine_s)
         self.num_timesteps = int(np.asarray(betas).shape[0])
         self.linear_start, self.linear_end = linear_start, linear_end
-        for k, v in schedules.ddpm_tables(betas).items():
+        for k, v in schedules.ddpm_tables(betas, v_posterior=self.v_posterior).items():
             self.register_buffer(k, torch.from_numpy(v))
+        self._anc_tabs = {}      # device coefficient tables of the ancestral update, per (device, clip, with noise)
 
     def init_from_ckpt(self, path, ignore_keys=list(), only_model=False):
         sd = torch.load(path, map_location="cpu")
@@ -741,6 +742,214 @@ class FridoDiffusion(_Base):
         if mix_tau != 0.:
             out[:, :ch_start] = (1 - mix_tau) * out[:, :ch_start] + mix_tau * noise[:, :ch_start]
         return out
+
+    # ---- ancestral (DDPM) sampling (frido.py:230-256,1226-1452) ---------------------------------------------------------
+    # The reference as shipped cannot run this branch (p_mean_variance reads a flag off the DiffusionWrapper that is not there, and the
+    # split head's eps has fewer channels than the latent the loops carry: tests/golden/ancestral_cfg.py).  What is built here is that
+    # code with the flag in place and the eps zero-padded to the latent's channels -- the reading under which its own lines are well-formed.
+    def _extract(self, name, t, x):
+        """extract_into_tensor (frido/modules/diffusionmodules/util.py): buffer[t] shaped (B, 1, 1, ...) for broadcasting against x."""
+        t = torch.as_tensor(t, device=x.device, dtype=torch.long)
+        return getattr(self, name).to(x.device).gather(-1, t).reshape(t.shape[0], *((1,) * (x.dim() - 1)))
+
+    def predict_start_from_noise(self, x_t, t, noise, ch_start=None, ch_end=None):
+        """frido.py:230-242: x_0 from x_t and eps; with ch_start only channels [ch_start, ch_end) are converted, the rest are x_t's.  Plain
+        tensor arithmetic on the inputs' device (a helper of the callers; the sampling path has it inside the update kernel)."""
+        a, b = self._extract("sqrt_recip_alphas_cumprod", t, x_t), self._extract("sqrt_recipm1_alphas_cumprod", t, x_t)
+        if ch_start is None:
+            return a * x_t - b * noise
+        out = x_t.clone()
+        out[:, ch_start:] = a * out[:, ch_start:] - b * noise[:, ch_start:]
+        if ch_end is not None:
+            out[:, ch_end:] = x_t[:, ch_end:]
+        return out
+
+    def q_posterior(self, x_start, x_t, t, ch_start=None, ch_end=None):
+        """frido.py:244-256: mean, variance and clipped log variance of q(x_{t-1} | x_t, x_0); outside [ch_start, ch_end) the mean is x_t."""
+        mean = self._extract("posterior_mean_coef1", t, x_t) * x_start + self._extract("posterior_mean_coef2", t, x_t) * x_t
+        if ch_start is not None:
+            mean[:, :ch_start] = x_t[:, :ch_start]
+            if ch_end is not None:
+                mean[:, ch_end:] = x_t[:, ch_end:]
+        return mean, self._extract("posterior_variance", t, x_t), self._extract("posterior_log_variance_clipped", t, x_t)
+
+    def _anc_refuse(self, cond=None, quantize_denoised=False, return_codebook_ids=False, mask=None, x0=None, loop=False):
+        if quantize_denoised:
+            raise NotImplementedError("quantize_denoised: `first_stage_model.quantize` does not exist on the MS-VQGAN (the reference raises an "
+                                      "AttributeError at frido.py:1256)")
+        if return_codebook_ids:
+            raise NotImplementedError("return_codebook_ids: the denoiser has no codebook-id head (predict_codebook_ids) on the HIP path; the "
+                                      "reference's p_sample raises 'Support dropped.' (frido.py:1278-1279)")
+        if mask is not None or x0 is not None:
+            raise NotImplementedError("mask / x0 (inpainting blend, frido.py:1405-1407): the sampler-step descriptor of ABI 7 has no room for the "
+                                      "blend's operands")
+        if loop and self.num_timesteps_cond > 1:
+            raise NotImplementedError("shorten_cond_schedule (num_timesteps_cond > 1, frido.py:1396-1399): the per-step q_sample of the conditioning "
+                                      "is not built")
+        if isinstance(cond, dict):
+            raise NotImplementedError("dict conditionings ('concat' / 'hybrid'): pass the cross-attention conditioning tensor or the class labels")
+        if not self.use_split_head:
+            raise NotImplementedError("ancestral sampling masks channels per stage, which needs use_split_head=True (every shipped Frido config)")
+
+    def _anc_host_tables(self):
+        """The five schedule buffers schedules.ancestral_table reads, as host arrays."""
+        return {k: getattr(self, k).detach().float().cpu().numpy() for k in (
+            "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "posterior_mean_coef1", "posterior_mean_coef2",
+            "posterior_log_variance_clipped")}
+
+    def _anc_table(self, device, clip, with_noise):
+        key = (str(device), bool(clip), bool(with_noise))
+        if key not in self._anc_tabs:
+            tab = schedules.ancestral_table(self._anc_host_tables(), clip_denoised=clip)
+            if not with_noise:
+                tab[:, 4] = 0.0          # p_mean_variance: x' = the posterior mean
+            self._anc_tabs[key] = torch.from_numpy(tab).to(device)
+        return self._anc_tabs[key]
+
+    def _anc_update(self, x, c, t, stage, clip_denoised, score_corrector, corrector_kwargs, noise=None, with_noise=False, temperature=1.,
+                    seed=0, sample0=0):
+        """Denoiser forward + ONE launch of the ancestral update kernel per distinct timestep: (x' or the posterior mean, x0)."""
+        if not x.is_cuda:
+            _no_cpu("FridoDiffusion.p_sample", x.device)
+        from .runtime import ancestral_step
+        stage = int(stage)
+        start, end = sum(self.embed_dim_list[:stage]), sum(self.embed_dim_list[:stage + 1])
+        assert end <= x.shape[1], f"stage {stage} needs a latent of at least {end} channels"
+        tl = [int(v) for v in torch.as_tensor(t).reshape(-1).tolist()]
+        assert len(tl) == x.shape[0] and all(0 <= v < self.num_timesteps for v in tl), "t: one timestep in [0, num_timesteps) per sample"
+        eps = self.apply_model(x, torch.as_tensor(t, device=x.device, dtype=torch.long), c, stage=stage)      # (B, end - start, H, W)
+        if score_corrector is not None:      # frido.py:1233-1241: the corrector sees the eps zero-padded to the latent's channels
+            B, C, H, W = x.shape
+            pad = torch.cat((x.new_zeros(B, start, H, W), eps, x.new_zeros(B, C - end, H, W)), dim=1)
+            eps = score_corrector.modify_score(self, pad, x, t, c, **(corrector_kwargs or {}))[:, start:end].float().contiguous()
+        unet = self.model.diffusion_model
+        return ancestral_step(unet.runtime().b, x.float(), eps, [self.num_timesteps - 1 - v for v in tl],
+                              self._anc_table(x.device, clip_denoised, with_noise), start, noise=noise, temperature=temperature, seed=seed,
+                              sample0=sample0, rng_stream=stage + 1)
+
+    @torch.no_grad()
+    def p_mean_variance(self, x, c, t, stage, clip_denoised: bool, return_codebook_ids=False, quantize_denoised=False, return_x0=False,
+                        score_corrector=None, corrector_kwargs=None):
+        """frido.py:1226-1265: (posterior mean, variance, clipped log variance[, x_recon]) -- denoiser forward and update kernel on the HIP
+        engine; the two variance factors are (B, 1, 1, 1) buffer lookups like the reference's."""
+        self._anc_refuse(c, quantize_denoised, return_codebook_ids)
+        mean, x0 = self._anc_update(x, c, t, stage, clip_denoised, score_corrector, corrector_kwargs)
+        var, logvar = self._extract("posterior_variance", t, x), self._extract("posterior_log_variance_clipped", t, x)
+        return (mean, var, logvar, x0) if return_x0 else (mean, var, logvar)
+
+    @torch.no_grad()
+    def p_sample(self, x, c, t, stage, clip_denoised=False, repeat_noise=False, return_codebook_ids=False, quantize_denoised=False,
+                 return_x0=False, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None, *, noise="torch", seed=0,
+                 sample0=0):
+        """frido.py:1267-1305: one ancestral step x_t -> x_{t-1} at `stage` (t may differ per sample: the kernel then goes out per sample).
+        noise: "torch" (default) draws like the reference -- one randn of x's shape from torch's CPU generator (repeat_noise: one sample's
+        worth, repeated), times temperature, then the dropout mask; a callable shape -> tensor replays a tape; "philox" draws in the kernel,
+        keyed by (seed, sample0 + b, num_timesteps - t, stage) -- the loops' key, so this call reproduces their draw at (t, stage)."""
+        self._anc_refuse(c, quantize_denoised, return_codebook_ids)
+        if not x.is_cuda:
+            _no_cpu("FridoDiffusion.p_sample", x.device)
+        nz = None
+        if noise == "philox":
+            if noise_dropout > 0. or repeat_noise:
+                raise NotImplementedError("noise_dropout / repeat_noise act on host noise: use noise='torch' (or a recorded tape)")
+        else:
+            draw = torch.randn if noise == "torch" else noise
+            shape = tuple(x.shape)
+            nz = draw((1,) + shape[1:]).repeat(shape[0], *((1,) * (len(shape) - 1))) if repeat_noise else draw(shape)      # noise_like
+            nz = torch.as_tensor(nz, dtype=torch.float32) * temperature
+            if noise_dropout > 0.:
+                nz = torch.nn.functional.dropout(nz, p=noise_dropout)
+            nz = nz.to(x.device)
+        out, x0 = self._anc_update(x, c, t, stage, clip_denoised, score_corrector, corrector_kwargs, noise=nz, with_noise=True,
+                                   temperature=float(temperature) if nz is None else 1.0, seed=seed, sample0=sample0)
+        return (out, x0) if return_x0 else out
+
+    def _anc_loop(self, cond, shape, T, what, *, noise, seed, sample0, collect, temperature=1., **kw):
+        """The loop on the SamplerEngine (kind="ddpm"): cached per (batch, latent shape, conditioning mode, T, clip, temperature) next to the
+        DDIM / PLMS engines of the denoiser, the whole call under the automatic plane selection."""
+        from . import autoplanes, samplers
+        from .runtime import SamplerEngine
+        unet = self.model.diffusion_model
+        B, C, H, W = (int(v) for v in shape)
+        if isinstance(cond, list):
+            raise NotImplementedError("list conditionings: pass the cross-attention conditioning tensor or the class labels")
+        if cond is not None and not isinstance(cond, dict) and not cond.is_cuda:
+            _no_cpu(what, cond.device)
+        mode = samplers.check_conditioning(unet, cond, B, name="cond")
+        if next(unet.parameters()).device.type != "cuda":
+            _no_cpu(what, next(unet.parameters()).device)
+        clip = bool(self.clip_denoised)
+        temp_key = float(temperature) if noise == "philox" else 1.0
+
+        def make(rt):      # only on an engine-cache miss: the posterior tables leave the device once per engine
+            return SamplerEngine(rt.builder_for(0), unet.cfg, B=B, C=C, H=H, W=W, nctx=mode if isinstance(mode, int) else 0, S=T, eta=0.,
+                                 kind="ddpm", alphas_cumprod=None, embed_dim=self.embed_dim_list, num_stage=self.num_resulotion,
+                                 temperature=temp_key, posterior=self._anc_host_tables(), clip=clip)
+
+        def go(noise_src):
+            rt = unet.runtime()
+            eng = samplers.cached_engine(rt, ("ddpm", B, C, H, W, mode, T, clip, temp_key), lambda: make(rt))
+            return eng.run_ancestral(cond, noise=noise_src, seed=seed, sample0=sample0, collect=collect, temperature=temperature,
+                                     model=self, **kw)
+        return autoplanes.run(unet, go, what, noise=noise)
+
+    @torch.no_grad()
+    def progressive_denoising(self, cond, shape, verbose=True, callback=None, quantize_denoised=False, img_callback=None, mask=None, x0=None,
+                              temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None, batch_size=None, x_T=None,
+                              start_T=None, log_every_t=None, *, noise="torch", seed=0, sample0=0):
+        """frido.py:1307-1363: the ancestral loop returning (img, the x0 predictions logged every log_every_t steps); `shape` excludes the
+        batch when batch_size is given; temperature: a float or one value per timestep."""
+        self._anc_refuse(cond, quantize_denoised, False, mask, x0, loop=True)
+        if not log_every_t:
+            log_every_t = self.log_every_t
+        if batch_size is not None:
+            shape = [batch_size] + list(shape)
+        else:
+            batch_size = shape[0]
+        if cond is not None and not isinstance(cond, dict):
+            cond = [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+        T = self.num_timesteps if start_T is None else min(self.num_timesteps, start_T)
+        return self._anc_loop(cond, shape, T, "FridoDiffusion.progressive_denoising", noise=noise, seed=seed, sample0=sample0, collect="x0",
+                              temperature=temperature, x_T=x_T, log_every_t=log_every_t, callback=callback, img_callback=img_callback,
+                              noise_dropout=noise_dropout, score_corrector=score_corrector, corrector_kwargs=corrector_kwargs)
+
+    @torch.no_grad()
+    def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, verbose=True, callback=None, timesteps=None,
+                      quantize_denoised=False, mask=None, x0=None, img_callback=None, start_T=None, log_every_t=None, *, noise="torch", seed=0,
+                      sample0=0):
+        """frido.py:1365-1418: for every stage, t = timesteps - 1 ... 0, one ancestral step of the full latent; `intermediates` starts with
+        x_T and gains the state at t % log_every_t == 0 or t == timesteps - 1, all stages in one list.  noise / seed / sample0: as for the
+        DDIM / PLMS samplers (frido_amd/samplers.py)."""
+        self._anc_refuse(cond, quantize_denoised, False, mask, x0, loop=True)
+        if not log_every_t:
+            log_every_t = self.log_every_t
+        T = self.num_timesteps if timesteps is None else timesteps
+        if start_T is not None:
+            T = min(T, start_T)
+        img, inter = self._anc_loop(cond, shape, int(T), "FridoDiffusion.p_sample_loop", noise=noise, seed=seed, sample0=sample0, collect="img",
+                                    x_T=x_T, log_every_t=log_every_t, callback=callback, img_callback=img_callback)
+        return (img, inter) if return_intermediates else img
+
+    @torch.no_grad()
+    def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, verbose=True, timesteps=None, quantize_denoised=False,
+               mask=None, x0=None, shape=None, **kwargs):
+        """frido.py:1420-1437.  Like the reference, only the named arguments reach p_sample_loop -- plus noise / seed / sample0 from kwargs."""
+        if shape is None:
+            shape = (batch_size, self.channels, self.image_size, self.image_size)
+        if cond is not None and not isinstance(cond, dict):
+            cond = [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+        extra = {k: kwargs[k] for k in ("noise", "seed", "sample0") if k in kwargs}
+        return self.p_sample_loop(cond, shape, return_intermediates=return_intermediates, x_T=x_T, verbose=verbose, timesteps=timesteps,
+                                  quantize_denoised=quantize_denoised, mask=mask, x0=x0, **extra)
+
+    @torch.no_grad()
+    def sample_log(self, cond, batch_size, ddim, ddim_steps, num_stage=1, **kwargs):
+        """frido.py:1439-1452: DDIM through DDIMSampler, otherwise the ancestral loop with its intermediates."""
+        if ddim:
+            from .samplers import DDIMSampler
+            shape = (self.channels, self.image_size, self.image_size)
+            return DDIMSampler(self).sample(ddim_steps, batch_size, shape, cond, num_stage=num_stage, verbose=False, **kwargs)
+        return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, **kwargs)
 
     def forward(self, *a, **k):
         raise FridoHipError("training (FridoDiffusion.forward / p_losses) is outside the inference hot path")

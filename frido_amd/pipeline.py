@@ -56,12 +56,24 @@ def sample_images(model, cond, *, S, eta=1.0, sampler="ddim", scale=1.0, uncond=
     turn a saturated fp16 operand plane or a non-finite normalisation statistic into a FridoNumericsWarning."""
     from .samplers import DDIMSampler, PLMSSampler
     unet = model.model.diffusion_model
-    cls = PLMSSampler if sampler == "plms" else DDIMSampler
     b = cond.shape[0]
     shape = (unet.in_channels, unet.image_size, unet.image_size)
-    z, _ = cls(model).sample(S=S, batch_size=b, shape=shape, conditioning=cond, num_stage=num_stage or unet.num_stage,
-                             eta=eta, verbose=False, unconditional_guidance_scale=scale, unconditional_conditioning=uncond,
-                             noise=noise, seed=seed, sample0=sample0, log_every_t=log_every_t)
+    if sampler == "ddpm":
+        # the ancestral loop (FridoDiffusion.p_sample_loop): S = chain length (t = S - 1 ... 0 per stage); it has no guidance, its noise
+        # level is the posterior's (what eta = 1 means to DDIM) and it always walks every stage of the model
+        if scale != 1.0 or uncond is not None:
+            raise ValueError("sampler='ddpm': the ancestral loop has no classifier-free guidance (scale must be 1.0, uncond None)")
+        if eta != 1.0:
+            raise ValueError(f"sampler='ddpm': the ancestral loop has no eta (got {eta}; leave it at 1.0)")
+        if num_stage is not None and num_stage != model.num_resulotion:
+            raise ValueError(f"sampler='ddpm': the ancestral loop runs all {model.num_resulotion} stages of the model (got num_stage={num_stage})")
+        z = model.p_sample_loop(cond, (b,) + shape, timesteps=S, verbose=False, log_every_t=log_every_t, noise=noise, seed=seed,
+                                sample0=sample0)
+    else:
+        cls = PLMSSampler if sampler == "plms" else DDIMSampler
+        z, _ = cls(model).sample(S=S, batch_size=b, shape=shape, conditioning=cond, num_stage=num_stage or unet.num_stage,
+                                 eta=eta, verbose=False, unconditional_guidance_scale=scale, unconditional_conditioning=uncond,
+                                 noise=noise, seed=seed, sample0=sample0, log_every_t=log_every_t)
     if gather_dtype == "float32":
         img = model.decode_first_stage(z)
     elif gather_dtype in ("uint8", "uint8_pil"):

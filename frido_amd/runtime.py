@@ -3,7 +3,9 @@
   DenoiserRuntime  — PyUNetModel.forward(x, t, context, stage) on the HIP engine (API path);
   SamplerEngine    — the multi-stage DDIM / PLMS loop with per-sample invariants hoisted, the per-step
                      body captured in a hipGraph, a device step counter and coefficient tables
-                     (reference: frido/models/diffusion/ddim.py:116-273, plms.py:116-303);
+                     (reference: frido/models/diffusion/ddim.py:116-273, plms.py:116-303); kind="ddpm": the
+                     ancestral loop of frido/models/diffusion/frido.py:1308-1418 on the same machinery;
+  ancestral_step   — one ancestral update outside a loop (FridoDiffusion.p_mean_variance / p_sample);
   DecoderRuntime   — VQModelInterface.decode / decode_first_stage on the HIP engine.
 """
 import os
@@ -14,7 +16,7 @@ import torch
 from . import _lib, config
 from .builder import Builder
 from .engine import current_stream_ptr, require_gpu
-from .schedules import sampler_coef_table
+from .schedules import ancestral_table, sampler_coef_table
 from .unet_plan import UNetStagePlan
 from .vqgan_plan import VQDecodePlan, VQEncodePlan
 
@@ -85,6 +87,48 @@ class DenoiserRuntime:
         return out
 
 
+@torch.no_grad()
+def ancestral_step(builder, x, eps, rows, coef, start, *, noise=None, temperature=1.0, seed=0, sample0=0, rng_stream=0):
+    """One ancestral (DDPM) update on the HIP kernel, outside a sampling loop (frido.py:1246-1258,1286-1305).
+    x (B, Cx, H, W) f32 NCHW on the GPU, eps (B, nch, H, W) the denoiser's output for channels [start, start + nch), rows: one row
+    index of the device table `coef` ([n][COEF_ROW], schedules.ancestral_table) per sample, noise (B, Cx, H, W) on the GPU or None
+    (Philox keyed by (seed, sample0 + b, row + 1, rng_stream)).  Samples that share a row go out in one launch; a non-uniform `t`
+    launches per sample.  Returns (x' NCHW, x0 NCHW).  The layout changes around the kernel are FRIDO_OP_RELAYOUT launches."""
+    B, Cx, H, W = x.shape
+    nch, HW, dev = eps.shape[1], H * W, x.device
+    with _lib.use_planes(builder.planes):
+        st = current_stream_ptr(dev)
+
+        def nhwc(t):
+            t = t.contiguous().float()
+            out = torch.empty(B, HW, t.shape[1], dtype=torch.float32, device=dev)
+            _run1(builder, "FRIDO_OP_RELAYOUT", st, src=t.data_ptr(), dst=out.data_ptr(), B=B, HW=HW, Csrc=t.shape[1], c0=0, Cuse=t.shape[1],
+                  Cdst=t.shape[1], d0=0, to_nchw=0)
+            return out
+
+        def nchw(t):
+            out = torch.empty(B, Cx, H, W, dtype=torch.float32, device=dev)
+            _run1(builder, "FRIDO_OP_RELAYOUT", st, src=t.data_ptr(), dst=out.data_ptr(), B=B, HW=HW, Csrc=Cx, c0=0, Cuse=Cx, Cdst=Cx, d0=0,
+                  to_nchw=1)
+            return out
+        xs, es = nhwc(x), nhwc(eps)
+        ns = nhwc(noise) if noise is not None else None
+        xo, p0 = torch.empty_like(xs), torch.empty_like(xs)
+        rows = [int(r) for r in rows]
+        assert len(rows) == B and all(0 <= r < coef.shape[0] for r in rows)
+        spans = [(0, B)] if len(set(rows)) == 1 else [(b, 1) for b in range(B)]
+        for b0, nb in spans:
+            off = b0 * HW * 4
+            kw = dict(x=xs.data_ptr() + off * Cx, B=nb, HW=HW, Cx=Cx, start=start, nch=nch, eps_cond=es.data_ptr() + off * nch,
+                      coef=coef.data_ptr(), coef_row_offset=rows[b0], temperature=float(temperature), x_out=xo.data_ptr() + off * Cx,
+                      pred_x0=p0.data_ptr() + off * Cx, write_x=1, seed=int(seed), sample0=int(sample0) + b0, rng_stream=int(rng_stream),
+                      hist_mode=_lib.STEP_ANCESTRAL)
+            if ns is not None:
+                kw.update(noise=ns.data_ptr() + off * Cx, noise_stride=0, noise_C=Cx, noise_c0=0)
+            _run1(builder, "FRIDO_OP_SAMPLER_STEP", st, **kw)
+        return nchw(xo), nchw(p0)
+
+
 class SamplerEngine:
     """One instance per (denoiser weights, B, latent shape, context length, S, eta, cfg on/off, kind)."""
 
@@ -94,7 +138,7 @@ class SamplerEngine:
             self._init(builder, cfg, **kw)
 
     def _init(self, builder: Builder, cfg, *, B, C, H, W, nctx, S, eta, kind, alphas_cumprod, embed_dim, cfg_scale=1.0,
-              use_graph=True, num_stage=None, temperature=1.0):
+              use_graph=True, num_stage=None, temperature=1.0, posterior=None, clip=False):
         self.b, self.cfg = builder, cfg
         self.dev = builder.device
         self.B, self.C, self.H, self.W, self.nctx = B, C, H, W, nctx
@@ -105,8 +149,16 @@ class SamplerEngine:
         self.num_stage = num_stage if num_stage is not None else cfg.get("num_stage", 1)
         self.use_graph = use_graph
         self.temperature = float(temperature)
-        tab, self.t_loop = sampler_coef_table(np.asarray(alphas_cumprod, dtype=np.float32), S, eta, plms=(kind == "plms"))
-        self.n_steps = tab.shape[0]
+        if kind == "ddpm":
+            # frido.py:1391-1394: every stage walks t = S - 1 ... 0 (S = num_timesteps, `timesteps=` or `start_T`); `posterior`: ddpm_tables' arrays
+            # The device table holds the WHOLE schedule (row r: t = num_timesteps - 1 - r) and a chain of S steps starts at row row0: the
+            # kernel's Philox draw index is its row + 1 = num_timesteps - t, whatever S is -- the key FridoDiffusion.p_sample uses too
+            tab, self.t_loop = ancestral_table(posterior, None, clip_denoised=clip), np.arange(S - 1, -1, -1)
+            assert 0 < S <= tab.shape[0], f"ancestral chain of {S} steps on a schedule of {tab.shape[0]}"
+            self.row0 = tab.shape[0] - S
+        else:
+            tab, self.t_loop = sampler_coef_table(np.asarray(alphas_cumprod, dtype=np.float32), S, eta, plms=(kind == "plms"))
+        self.n_steps = S if kind == "ddpm" else tab.shape[0]
         self.coef = torch.from_numpy(tab).to(self.dev)
         self.step = torch.zeros(1, dtype=torch.int32, device=self.dev)
         # class-conditional denoisers: the embedding table has one row per (step, sample); this counter advances by Bx per step
@@ -136,6 +188,13 @@ class SamplerEngine:
             self.hist_stride = B * H * W * nmax
             self.hist = torch.zeros(4, self.hist_stride, dtype=torch.float32, device=self.dev)    # eps ring, slot = step & 3
             self.x_save = torch.zeros_like(self.x)
+        if kind == "ddpm":
+            # host-noise form: the tape and the coefficient rows of ONE replay unit (up to GRAPH_STEPS steps), read through a counter of
+            # their own that restarts with every unit -- a T = 1000 tape of a whole stage would be gigabytes at B = 16
+            self.unit = GRAPH_STEPS if use_graph else 1
+            self.step_c = torch.zeros(1, dtype=torch.int32, device=self.dev)
+            self.coef_c = torch.zeros(self.unit, tab.shape[1], dtype=torch.float32, device=self.dev)
+            self.tape = None
 
     # ---- helpers ---------------------------------------------------------------------------------
     def _stream_ptr(self):
@@ -201,6 +260,7 @@ class SamplerEngine:
         step by step on the stream (forward program, hook on torch tensors, update kernel) instead of replaying a captured graph.
         Returns (samples NCHW, intermediates dict)."""
         B, C, H, W = self.B, self.C, self.H, self.W
+        assert self.kind != "ddpm", "an ancestral engine runs through run_ancestral()"
         self._opts = dict(noise_dropout=float(noise_dropout), score_corrector=score_corrector, corrector_kwargs=dict(corrector_kwargs or {}),
                           model=model, cond=cond, uncond=uncond)
         if noise_dropout > 0. and noise == "philox":
@@ -489,6 +549,167 @@ class SamplerEngine:
                         torch.nn.functional.dropout(nz, p=p_drop)      # (plms.py get_x_prev_and_pred_x0: the mask draw consumes generator state)
             go(g_first if i == 0 else g_body)
             self._log(s, i, inter, log_every_t, sp, Cs, callback, img_callback)
+
+
+    # ---- ancestral (DDPM) loop ---------------------------------------------------------------------------
+    @torch.no_grad()
+    @_lib.with_planes
+    def run_ancestral(self, cond, *, x_T=None, noise="torch", seed=0, sample0=0, log_every_t=100, callback=None, img_callback=None,
+                      temperature=1.0, noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, model=None, collect="img"):
+        """frido.py:1366-1418 (p_sample_loop; collect="img") / :1308-1363 (progressive_denoising; collect="x0"): for every stage, t = T - 1 ... 0,
+        one ancestral update of the FULL latent -- no hand-off between the stages, x_T (when given) is the start of stage 0.
+        noise: "torch" draws from torch's CPU generator in the reference's order (x_T, then per step one full-shape randn -- t = 0 included --
+        and, with noise_dropout, its keep mask); a callable shape -> tensor replays a tape the same way; "philox" draws in the kernel, keyed
+        by (seed, global sample index, num_timesteps - t, stage) -- p_sample's key, so one p_sample call reproduces the loop's draw at that
+        (t, stage) whatever the chain length.  temperature: a float, or the reference's per-timestep list (host noise only: the
+        product noise * temperature[t] is formed on the host, where the reference forms it).  Captured step bodies are replayed in units
+        of up to GRAPH_STEPS steps; a step whose result is logged ends its unit; callbacks make every unit one step long; a score corrector
+        runs forward program, hook and update kernel eagerly.  Returns (img NCHW, list of logged tensors)."""
+        B, C, H, W, n = self.B, self.C, self.H, self.W, self.n_steps
+        if noise_dropout > 0. and noise == "philox":
+            raise NotImplementedError("noise_dropout draws its keep mask from torch's generator: use noise='torch' (or a recorded tape)")
+        draw = (lambda shape: torch.randn(shape)) if noise == "torch" else (noise if callable(noise) else None)
+        if isinstance(temperature, (list, tuple)):
+            if draw is None:
+                raise NotImplementedError("a per-timestep temperature list needs host noise (noise='torch' or a tape): the Philox form multiplies in the kernel by one scalar")
+            temps = [float(v) for v in temperature]
+            assert len(temps) >= n, "temperature: one entry per timestep"
+        else:
+            temps = [float(temperature)] * n
+            assert draw is not None or float(temperature) == self.temperature, "the Philox form bakes its temperature into the engine"
+        opts = dict(noise_dropout=float(noise_dropout), score_corrector=score_corrector, corrector_kwargs=dict(corrector_kwargs or {}),
+                    model=model, cond=cond, temps=temps)
+        stream = self._stream_ptr()
+        stream.wait_stream(torch.cuda.current_stream(self.dev))
+        sp = stream.cuda_stream
+        with torch.cuda.stream(stream):
+            ctx = cond.to(self.dev, torch.float32 if not self.labels or cond.is_floating_point() else torch.int64) if cond is not None else None
+            if x_T is not None:
+                xt = torch.as_tensor(x_T, dtype=torch.float32)
+            else:
+                xt = draw((B, C, H, W)) if draw is not None else None
+            if xt is not None:
+                xd = torch.as_tensor(xt, dtype=torch.float32).to(self.dev).contiguous()
+                assert xd.shape == (B, C, H, W), (tuple(xd.shape), (B, C, H, W))
+                _run1(self.b, "FRIDO_OP_RELAYOUT", sp, src=xd.data_ptr(), dst=self.x.data_ptr(), B=B, HW=H * W, Csrc=C, c0=0, Cuse=C, Cdst=C,
+                      d0=0, to_nchw=0)
+            else:
+                _run1(self.b, "FRIDO_OP_RANDN", sp, dst=self.x.data_ptr(), n=B * H * W * C, per_sample=H * W * C, seed=seed, sample0=sample0,
+                      rng_stream=0)
+            inter = [self._to_nchw(self.x, sp)] if collect == "img" else []
+            t_loop = torch.from_numpy(self.t_loop.astype(np.int64)).to(self.dev)
+            self.rng.copy_(torch.tensor([seed, sample0], dtype=torch.int64))
+            for s in range(self.num_stage):
+                plan = self.stages[s]
+                if self.labels:
+                    plan.set_labels(ctx)
+                elif ctx is not None:
+                    plan.set_context(ctx)
+                plan.set_timesteps(t_loop)
+                self.step.zero_()
+                if self.labels:
+                    self.step_bx.zero_()
+                plan.pre.run(sp)
+                self._ddpm_stage(s, sp, draw, inter, log_every_t, callback, img_callback, opts, collect)
+            out = self._to_nchw(self.x, sp)
+        torch.cuda.current_stream(self.dev).wait_stream(stream)
+        return out, inter
+
+    def _ancestral_op(self, s, tape):
+        B, HW, C = self.B, self.H * self.W, self.C
+        kw = dict(x=self.x.data_ptr(), B=B, HW=HW, Cx=C, start=sum(self.embed[:s]), nch=self.embed[s], eps_cond=self.stages[s].eps.data_ptr(),
+                  x_out=self.x.data_ptr(), pred_x0=self.pred_x0.data_ptr(), write_x=1, hist_mode=_lib.STEP_ANCESTRAL)
+        if tape:      # this unit's noise (already multiplied by its temperature) and coefficient rows, by the unit's own counter
+            kw.update(coef=self.coef_c.data_ptr(), step=self.step_c.data_ptr(), temperature=1.0, noise=self.tape.data_ptr(),
+                      noise_stride=B * HW * C, noise_C=C, noise_c0=0)
+        else:
+            kw.update(coef=self.coef.data_ptr(), coef_row_offset=self.row0, step=self.step.data_ptr(), temperature=self.temperature,
+                      rng_stream=s + 1, rng_dev=self.rng.data_ptr())
+        return kw
+
+    def _ddpm_stage(self, s, sp, draw, inter, log_every_t, callback, img_callback, opts, collect):
+        from .engine import Prog
+        plan = self.stages[s]
+        n, B, C, H, W = self.n_steps, self.B, self.C, self.H, self.W
+        tape = draw is not None
+        if tape and self.tape is None:
+            self.tape = torch.empty(self.unit, B, H, W, C, dtype=torch.float32, device=self.dev)
+        corrector = opts["score_corrector"] is not None
+
+        def update_ops(p):
+            p.emit("FRIDO_OP_SAMPLER_STEP", **self._ancestral_op(s, tape))
+            self._step_add(p, 1)
+            if tape:
+                p.emit("FRIDO_OP_STEP_ADD", step=self.step_c.data_ptr(), delta=1)
+        key = ("ddpm_tape" if tape else "ddpm", s)
+        if corrector:
+            upd = Prog(self.dev, self.b.nsplit)
+            update_ops(upd)
+        elif key not in self.graphs:
+            body = Prog(self.dev, self.b.nsplit)
+            body.ops = list(plan.step.ops)
+            update_ops(body)
+            body.keep = [plan]
+            self.graphs[key] = body.capture(sp) if self.use_graph else body
+            self.graph_captures = getattr(self, "graph_captures", 0) + 1
+        K = self.unit if (self.use_graph and not corrector and callback is None and img_callback is None) else 1
+        gk = None
+        if K > 1 and n >= K:
+            kkey = key + ("x%d" % K,)
+            if kkey not in self.graphs:
+                multi = Prog(self.dev, self.b.nsplit)
+                multi.ops = list(self.graphs[key].keep[1].ops) * K
+                multi.keep = [plan]
+                self.graphs[kkey] = multi.capture(sp)
+                self.graph_captures = getattr(self, "graph_captures", 0) + 1
+            gk = self.graphs[kkey]
+        logged = lambda i: (n - 1 - i) % log_every_t == 0 or i == 0          # frido.py:1409: i % log_every_t == 0 or i == timesteps - 1, i = t
+        p_drop = opts["noise_dropout"]
+        i = 0
+        while i < n:
+            unit = K if (gk is not None and i + K <= n and not any(logged(j) for j in range(i, i + K - 1))) else 1
+            if tape:
+                rows = []
+                for j in range(i, i + unit):
+                    nz = torch.as_tensor(draw((B, C, H, W)), dtype=torch.float32) * opts["temps"][n - 1 - j]      # frido.py:1286
+                    rows.append(torch.nn.functional.dropout(nz, p=p_drop) if p_drop > 0. else nz)                 # frido.py:1288-1289
+                self.tape[:unit].copy_(torch.stack(rows).permute(0, 1, 3, 4, 2))                                  # plumbing: layout + H2D
+                self.coef_c[:unit].copy_(self.coef[self.row0 + i:self.row0 + i + unit])
+                self.step_c.zero_()
+            if corrector:
+                plan.step.run(sp)
+                self._corrected_eps_full(s, sp, int(self.t_loop[i]), opts)
+                upd.run(sp)
+            elif unit > 1:
+                gk.launch(sp)
+                self.multi_step_launches = getattr(self, "multi_step_launches", 0) + 1
+            elif self.use_graph:
+                self.graphs[key].launch(sp)
+            else:
+                self.graphs[key].run(sp)
+            i += unit
+            t = n - i
+            if logged(i - 1):
+                inter.append(self._to_nchw(self.x if collect == "img" else self.pred_x0, sp))
+            if callback:
+                callback(t)
+            if img_callback:
+                img_callback(self._to_nchw(self.x, sp), t)
+
+    def _corrected_eps_full(self, s, sp, t_value, opts):
+        """frido.py:1233-1241: the split head's eps zero-padded to the latent's channels, `score_corrector.modify_score(model, model_out, x, t,
+        c, **kwargs)` on torch tensors (NCHW), the stage's channels written back as the eps the update kernel reads."""
+        plan = self.stages[s]
+        B, C, H, W = self.B, self.C, self.H, self.W
+        start, nch = sum(self.embed[:s]), self.embed[s]
+        e = plan.eps.view(B, H, W, nch).permute(0, 3, 1, 2)
+        e_t = torch.cat((torch.zeros(B, start, H, W, device=self.dev), e, torch.zeros(B, C - start - nch, H, W, device=self.dev)), dim=1)
+        t = torch.full((B,), int(t_value), device=self.dev, dtype=torch.long)
+        e_new = opts["score_corrector"].modify_score(opts["model"], e_t, self._to_nchw(self.x, sp), t, opts["cond"], **opts["corrector_kwargs"])
+        e_new = e_new.to(torch.float32).contiguous()
+        assert e_new.shape == (B, C, H, W), "modify_score must return a tensor of model_out's shape"
+        _run1(self.b, "FRIDO_OP_RELAYOUT", sp, src=e_new.data_ptr(), dst=plan.eps.data_ptr(), B=B, HW=H * W, Csrc=C, c0=start, Cuse=nch,
+              Cdst=nch, d0=0, to_nchw=0)
 
 
 class DecoderRuntime:

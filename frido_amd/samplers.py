@@ -18,6 +18,45 @@ from . import schedules
 from ._lib import FridoHipError
 
 
+def check_conditioning(unet, conditioning, batch_size, name="conditioning"):
+    """What every sampling loop (DDIM / PLMS `sample`, the ancestral loops) asks of its conditioning before it plans anything; returns
+    the engine-cache mode: the context length, "labels" or "uncond"."""
+    has_ctx = getattr(unet, "use_spatial_transformer", True)
+    labels = getattr(unet, "num_classes", None) is not None
+    if isinstance(conditioning, dict):
+        raise NotImplementedError("dict conditionings ('concat' / 'hybrid'): pass the cross-attention conditioning tensor or the class labels")
+    if conditioning is None:
+        if has_ctx:
+            raise NotImplementedError("cross-attention conditioning tensor required")
+        if labels:
+            raise ValueError(f"a class-conditional denoiser needs its labels as `{name}`")
+        return "uncond"
+    if not has_ctx and not labels:
+        raise ValueError(f"this denoiser takes neither a context nor class labels: pass {name}=None")
+    if conditioning.shape[0] != batch_size:
+        # the reference only prints a warning here (ddim.py:87-93) and then fails (or silently broadcasts) inside the
+        # denoiser; a mismatched batch is never what the caller meant
+        raise ValueError(f"Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
+    if labels:
+        want = (batch_size,) if unet.use_embed else (batch_size, unet.num_classes)
+        if tuple(conditioning.shape) != want:
+            raise ValueError(f"class labels of shape {tuple(conditioning.shape)}: this denoiser takes {want}")
+    return conditioning.shape[1] if has_ctx else "labels"
+
+
+def cached_engine(rt, key, make):
+    """The denoiser runtime's least-recently-used cache of SamplerEngines, shared by every sampler kind: `make()` builds a missing one."""
+    cache = rt.__dict__.setdefault("_sampler_engines", collections.OrderedDict())
+    if key in cache:
+        cache.move_to_end(key)
+    else:
+        while len(cache) >= ENGINE_CACHE_SIZE:      # least-recently-used engine goes; it owns its plans' persistent buffers
+            # (Builder.persist_scope) and graphs, so its HBM is released with it -- the activation pool is shared and reused
+            cache.popitem(last=False)
+        cache[key] = make()
+    return cache[key]
+
+
 class _SamplerBase:
     KIND = "ddim"
 
@@ -46,18 +85,10 @@ class _SamplerBase:
         rt = unet.runtime()
         C, H, W = shape
         key = (self.KIND, B, C, H, W, nctx, S, float(eta), scale != 1.0, num_stage, float(temperature), replica)
-        cache = rt.__dict__.setdefault("_sampler_engines", collections.OrderedDict())
-        if key in cache:
-            cache.move_to_end(key)
-        else:
-            while len(cache) >= ENGINE_CACHE_SIZE:      # least-recently-used engine goes; it owns its plans' persistent buffers
-                # (Builder.persist_scope) and graphs, so its HBM is released with it -- the activation pool is shared and reused
-                cache.popitem(last=False)
-            cache[key] = SamplerEngine(rt.builder_for(replica), unet.cfg, B=B, C=C, H=H, W=W, nctx=nctx if isinstance(nctx, int) else 0, S=S, eta=eta, kind=self.KIND,
-                                       alphas_cumprod=self.model.alphas_cumprod.detach().float().cpu().numpy(),
-                                       embed_dim=self.model.embed_dim_list, cfg_scale=scale, num_stage=num_stage,
-                                       temperature=temperature)
-        eng = cache[key]
+        eng = cached_engine(rt, key, lambda: SamplerEngine(
+            rt.builder_for(replica), unet.cfg, B=B, C=C, H=H, W=W, nctx=nctx if isinstance(nctx, int) else 0, S=S, eta=eta, kind=self.KIND,
+            alphas_cumprod=self.model.alphas_cumprod.detach().float().cpu().numpy(), embed_dim=self.model.embed_dim_list, cfg_scale=scale,
+            num_stage=num_stage, temperature=temperature))
         eng.cfg_scale = float(scale)      # read from a device scalar by the captured step bodies: one graph, any scale
         return eng
 
@@ -76,35 +107,17 @@ class _SamplerBase:
         if quantize_x0:
             raise NotImplementedError("quantize_x0: the reference calls exit() on this option (ddim.py:251-253)")
         unet = getattr(getattr(self.model, "model", None), "diffusion_model", None)
-        has_ctx = getattr(unet, "use_spatial_transformer", True)
-        labels = getattr(unet, "num_classes", None) is not None
-        if isinstance(conditioning, dict):
-            raise NotImplementedError("dict conditionings ('concat' / 'hybrid'): pass the cross-attention conditioning tensor or the class labels")
+        # engine-cache key: context length, or which conditioning mode the plans were built for
+        mode = check_conditioning(unet, conditioning, batch_size)
         if conditioning is None:
-            if has_ctx:
-                raise NotImplementedError("cross-attention conditioning tensor required")
-            if labels:
-                raise ValueError("a class-conditional denoiser needs its labels as `conditioning`")
             if unconditional_guidance_scale != 1.:
                 raise ValueError("classifier-free guidance needs a conditioning")
         else:
-            if not has_ctx and not labels:
-                raise ValueError("this denoiser takes neither a context nor class labels: pass conditioning=None")
-            if conditioning.shape[0] != batch_size:
-                # the reference only prints a warning here (ddim.py:87-93) and then fails (or silently broadcasts) inside the
-                # denoiser; a mismatched batch is never what the caller meant
-                raise ValueError(f"Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
-            if labels:
-                want = (batch_size,) if unet.use_embed else (batch_size, unet.num_classes)
-                if tuple(conditioning.shape) != want:
-                    raise ValueError(f"class labels of shape {tuple(conditioning.shape)}: this denoiser takes {want}")
             if unconditional_conditioning is not None and unconditional_conditioning.shape != conditioning.shape:
                 raise ValueError(f"unconditional_conditioning {tuple(unconditional_conditioning.shape)} must match "
                                  f"conditioning {tuple(conditioning.shape)}")
             if not conditioning.is_cuda:
                 raise FridoHipError("sample(): conditioning must live on the MI355X (there is no CPU path)")
-        # engine-cache key: context length, or which conditioning mode the plans were built for
-        mode = conditioning.shape[1] if has_ctx else ("labels" if labels else "uncond")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         if unconditional_guidance_scale != 1.:
             assert unconditional_conditioning is not None

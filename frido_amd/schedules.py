@@ -3,13 +3,14 @@
 Restates, with the reference's exact float32/float64 mix so tables are bit-identical
 (pinned by tests/golden/schedules.npz):
   frido/modules/diffusionmodules/util.py:21-26   make_beta_schedule('linear')
-  frido/models/diffusion/frido.py:127-155        register_schedule (float64 cumprod -> float32 buffers)
+  frido/models/diffusion/frido.py:127-168        register_schedule (float64 cumprod -> float32 buffers, posterior q(x_{t-1} | x_t, x_0))
   frido/modules/diffusionmodules/util.py:46-74   make_ddim_timesteps / make_ddim_sampling_parameters
   frido/models/diffusion/ddim.py:25-54           DDIMSampler.make_schedule
 """
 import numpy as np
 
 COEF_ROW = 12   # must match csrc/misc.hip: a_t, a_prev, sigma, sqrt(1-a_t), ab0..ab3, den, pad
+                # (FRIDO_STEP_ANCESTRAL rows: sqrt_recip_ac, sqrt_recipm1_ac, post_coef1, post_coef2, sigma, clip, pad)
 
 
 def _linspace(start, end, steps):
@@ -41,17 +42,47 @@ def make_beta_schedule(schedule, n_timestep, linear_start=1e-4, linear_end=2e-2,
     raise ValueError(f"schedule '{schedule}' unknown.")
 
 
-def ddpm_tables(betas):
-    """The float32 buffers DDPM.register_schedule registers (inference subset)."""
+def ddpm_tables(betas, v_posterior=0.):
+    """The float32 buffers DDPM.register_schedule registers (inference subset), the posterior q(x_{t-1} | x_t, x_0) of frido.py:157-168
+    included: float64 arithmetic in the reference's order of operations, one cast to float32 at the end."""
     betas = np.asarray(betas, dtype=np.float64)
     alphas = 1.0 - betas
     ac = np.cumprod(alphas, axis=0)
     ac_prev = np.append(1.0, ac[:-1])
     f32 = lambda a: np.asarray(a, dtype=np.float32)
+    post_var = (1 - v_posterior) * betas * (1. - ac_prev) / (1. - ac) + v_posterior * betas
     return dict(betas=f32(betas), alphas_cumprod=f32(ac), alphas_cumprod_prev=f32(ac_prev),
                 sqrt_alphas_cumprod=f32(np.sqrt(ac)), sqrt_one_minus_alphas_cumprod=f32(np.sqrt(1.0 - ac)),
                 log_one_minus_alphas_cumprod=f32(np.log(1.0 - ac)), sqrt_recip_alphas_cumprod=f32(np.sqrt(1.0 / ac)),
-                sqrt_recipm1_alphas_cumprod=f32(np.sqrt(1.0 / ac - 1)))
+                sqrt_recipm1_alphas_cumprod=f32(np.sqrt(1.0 / ac - 1)),
+                posterior_variance=f32(post_var),
+                # (clipped: the posterior variance is 0 at t = 0)
+                posterior_log_variance_clipped=f32(np.log(np.maximum(post_var, 1e-20))),
+                posterior_mean_coef1=f32(betas * np.sqrt(ac_prev) / (1. - ac)),
+                posterior_mean_coef2=f32((1. - ac_prev) * np.sqrt(alphas) / (1. - ac)))
+
+
+def ancestral_table(tables, T=None, clip_denoised=False):
+    """float32 table [T][COEF_ROW] of the ancestral (DDPM) update in LOOP order -- row i is the step at t = T - 1 - i, the order of
+    `reversed(range(T))` in frido.py:1391-1394 -- for FridoSamplerStep.hist_mode = FRIDO_STEP_ANCESTRAL:
+    {sqrt_recip_alphas_cumprod[t], sqrt_recipm1_alphas_cumprod[t], posterior_mean_coef1[t], posterior_mean_coef2[t],
+     sigma = (t != 0) * exp(0.5 * posterior_log_variance_clipped[t]) (fp32, frido.py:1291,1305), clip (0 / 1), pad}.
+    tables: ddpm_tables' dict (or any mapping of the same float32 arrays); T <= len(betas): the chain starts at t = T - 1 (`timesteps=` /
+    `start_T` of p_sample_loop)."""
+    get = lambda k: np.asarray(tables[k], dtype=np.float32)
+    n = get("posterior_mean_coef1").shape[0]
+    T = n if T is None else int(T)
+    assert 0 < T <= n, f"ancestral_table: T = {T} outside 1 .. {n}"
+    t = np.arange(T - 1, -1, -1)
+    tab = np.zeros((T, COEF_ROW), dtype=np.float32)
+    tab[:, 0] = get("sqrt_recip_alphas_cumprod")[t]
+    tab[:, 1] = get("sqrt_recipm1_alphas_cumprod")[t]
+    tab[:, 2] = get("posterior_mean_coef1")[t]
+    tab[:, 3] = get("posterior_mean_coef2")[t]
+    half = (np.float32(0.5) * get("posterior_log_variance_clipped")[t]).astype(np.float32)
+    tab[:, 4] = np.exp(half.astype(np.float64)).astype(np.float32) * (t != 0)
+    tab[:, 5] = 1.0 if clip_denoised else 0.0
+    return tab
 
 
 def make_ddim_timesteps(method, num_ddim, num_ddpm):

@@ -40,7 +40,8 @@ typedef uint16_t frido_bf16;
  * GroupNorm-apply input gn_*), two-plane operand producers saturate at +-65504.  4 (r04): FridoGemm.sk_mode 2 + FridoGnApply.sk_* at the
  * struct's END (a split-K GEMM's reduction finished by the GroupNorm launch that consumes its output).  5 (r05): FridoAttnSmall.skip_act_store
  * at the struct's END; frido_status_flags(&word, clear) (sticky saturation / non-finite flags; clear = 1 resets them).
- * 7: the multi-head flash attention descriptor FridoAttnMh, its launcher frido_attn_mh and the op kind FRIDO_OP_ATTN_MH were ADDED (no existing struct moved). */
+ * 7: the multi-head flash attention descriptor FridoAttnMh, its launcher frido_attn_mh and the op kind FRIDO_OP_ATTN_MH were ADDED (no existing struct moved).
+ * 7, no layout change: FridoSamplerStep.hist_mode gained the VALUE FRIDO_STEP_ANCESTRAL (the DDPM ancestral update; every other mode computes the same bits). */
 #define FRIDO_ABI_VERSION 7
 #define FRIDO_SPLITK_HEADER_BYTES 65536     /* the ticket header at the start of a split-K workspace; partial sums follow: [splitk][M][N] f32 */
 
@@ -354,6 +355,22 @@ typedef struct FridoSamplerStep {
     const float* cfg_dev;
     float* hist_ring; int64_t hist_stride; int32_t hist_mode;
 } FridoSamplerStep;
+/* hist_mode == FRIDO_STEP_ANCESTRAL (a value, not a flag: it cannot be mistaken for the ring modes 1 / 3): the same descriptor carries
+ * ONE ancestral (DDPM) update, p_mean_variance + p_sample of frido/models/diffusion/frido.py:1246-1258,1286-1305 with
+ * predict_start_from_noise / q_posterior (:230-256), expression for expression in fp32:
+ *   x0   = c_recip * x - c_recipm1 * eps   on the active channels [start, start + nch), x0 = x elsewhere;
+ *   x0   = clamp(x0, -1, 1) on EVERY channel when the row's clip flag is set (x_recon.clamp_ is in place on the whole tensor);
+ *   mean = coef1 * x0 + coef2 * x          on the active channels, mean = x elsewhere;
+ *   x'   = mean + sigma * (noise * temperature), noise zeroed on channels [0, start) ONLY (with the split head the reference zeroes
+ *          nothing else: at stage 0 every channel of the state receives noise).
+ * The 12-float row coef[*step + coef_row_offset] then means {sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, posterior_mean_coef1,
+ * posterior_mean_coef2, sigma = (t != 0) * exp(0.5 * posterior_log_variance_clipped), clip (0 / 1), pad ...}.  Requirements:
+ * hist_ring, eps_uncond, eps_out and hist1..3 NULL; HW * Cx a multiple of 4 and x / x_out / pred_x0 / noise 16-byte aligned (the kernel
+ * makes one pass of 16-byte accesses over the state); a noise tape spans channels [noise_c0, Cx) (noise_C == Cx - noise_c0,
+ * noise_c0 <= start).  Without a tape the noise is Philox4x32-10 keyed by (seed, global sample index, *step + coef_row_offset + 1,
+ * rng_stream), its 4-float groups numbered over the flat sample [HW][Cx] -- frido_randn's numbering with per_sample = HW * Cx.
+ * pred_x0 receives x0 (all Cx channels).  A non-finite x' raises FRIDO_STATUS_NONFINITE. */
+#define FRIDO_STEP_ANCESTRAL 16
 
 /* Stage hand-off (ddim.py:177-185): channels [c0,c1) of x[B][H][W][Cx] replaced by their
  * 2^levels x 2^levels block mean (avg_pool2d applied `levels` times, then nearest expand). */
