@@ -174,20 +174,20 @@ extern "C" int frido_run_timed(const FridoOp* ops, int32_t n, frido_stream_t s, 
     return rc;
 }
 
-extern "C" int frido_graph_capture(const FridoOp* ops, int32_t n, frido_stream_t s, void** out) {
-    if (!ops || n <= 0 || !out) {
-        frido_set_error("frido_graph_capture: bad arguments");
-        return FRIDO_EINVAL;
-    }
-    hipStream_t st = (hipStream_t)s;
-    hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+extern "C" int frido_capture_begin(frido_stream_t s) {
+    hipError_t e = hipStreamBeginCapture((hipStream_t)s, hipStreamCaptureModeThreadLocal);
     if (e != hipSuccess) {
         frido_set_error("hipStreamBeginCapture: %s", hipGetErrorString(e));
         return FRIDO_EHIP;
     }
-    int rc = frido_run(ops, n, s);
+    return FRIDO_OK;
+}
+
+namespace {
+// ends the capture on `st`; `rc` is the status of what was launched inside it (a failed body still has to end its capture)
+int capture_finish(hipStream_t st, int rc, void** out) {
     Graph* g = new Graph();
-    e = hipStreamEndCapture(st, &g->graph);
+    hipError_t e = hipStreamEndCapture(st, &g->graph);
     if (rc != FRIDO_OK || e != hipSuccess) {
         if (e != hipSuccess) frido_set_error("hipStreamEndCapture: %s", hipGetErrorString(e));
         if (g->graph) (void)hipGraphDestroy(g->graph);
@@ -203,6 +203,26 @@ extern "C" int frido_graph_capture(const FridoOp* ops, int32_t n, frido_stream_t
     }
     *out = g;
     return FRIDO_OK;
+}
+}  // namespace
+
+extern "C" int frido_capture_end(frido_stream_t s, void** out) {
+    if (!out) {
+        frido_set_error("frido_capture_end: bad arguments");
+        return FRIDO_EINVAL;
+    }
+    return capture_finish((hipStream_t)s, FRIDO_OK, out);
+}
+
+extern "C" int frido_graph_capture(const FridoOp* ops, int32_t n, frido_stream_t s, void** out) {
+    if (!ops || n <= 0 || !out) {
+        frido_set_error("frido_graph_capture: bad arguments");
+        return FRIDO_EINVAL;
+    }
+    int rc = frido_capture_begin(s);
+    if (rc != FRIDO_OK) return rc;
+    rc = frido_run(ops, n, s);
+    return capture_finish((hipStream_t)s, rc, out);
 }
 
 extern "C" int frido_graph_launch(void* graph, frido_stream_t s) {

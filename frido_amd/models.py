@@ -661,7 +661,16 @@ class FridoDiffusion(_Base):
         return z.clone()
 
     def apply_model(self, x_noisy, t, cond, stage=None, return_ids=False):
-        """frido.py:1062-1160 (no split_input_params)."""
+        """frido.py:1062-1160.  With `split_input_params` set (looked up on every call, like the reference's hasattr) the patch-wise
+        branch of :1076-1152 runs: x_noisy is cut into overlapping crops (frido_unfold), the denoiser runs ONCE on the B * L crop batch
+        (timesteps, context / labels repeated per crop), and the eps is stitched back with the border-distance weighting (frido_fold)."""
+        from . import patching
+        patch = patching.params_of(self)
+        if patch is not None:
+            if return_ids:
+                raise ValueError("apply_model(return_ids=True) with split_input_params set: the reference asserts `not return_ids` (frido.py:1078)")
+            patching.check_conditioning(self, cond)
+            return self._apply_model_patches(x_noisy, t, cond, stage, patch)
         if not isinstance(cond, dict):
             if not isinstance(cond, list):
                 cond = [cond]
@@ -669,10 +678,30 @@ class FridoDiffusion(_Base):
         out = self.model(x_noisy, t, stage=stage, **cond)
         return out[0] if isinstance(out, tuple) and not return_ids else out
 
+    def _apply_model_patches(self, x_noisy, t, cond, stage, patch):
+        from . import patching
+        from .runtime import patch_fold, patch_unfold
+        B, _, H, W = x_noisy.shape
+        geo = patching.geometry(patch, H, W, patching.MODEL, x_noisy.device)      # raises for a geometry the reference cannot stitch
+        if not x_noisy.is_cuda:
+            _no_cpu("FridoDiffusion.apply_model", x_noisy.device)
+        unet = self.model.diffusion_model
+        # the builder only launches layout changes and the two patch kernels, which are the same code in both builds of the library: should
+        # the automatic plane selection move the denoiser to another runtime during the forward below, folding on this one is still right
+        b = unet.runtime().b
+        crops = patch_unfold(b, geo, x_noisy.float())                                  # (B * L, C, kh, kw), crop l of sample b at b * L + l
+        per_crop = lambda v: None if v is None else v.repeat_interleave(geo.L, dim=0)
+        t = torch.as_tensor(t, device=x_noisy.device, dtype=torch.long).reshape(-1)
+        out = self.model(crops, per_crop(t), stage=stage, c_crossattn=[per_crop(cond)])      # cond None: [None], like the whole-latent path
+        assert not isinstance(out, tuple), "the patch-wise mode cannot deal with multiple model outputs (frido.py:1144-1145)"
+        return patch_fold(b, geo, out, B)
+
     @torch.no_grad()
     def decode_first_stage(self, z_in, predict_cids=False, force_not_quantize=False, return_code=False, to_uint8=False,
                            force_codes=None):
-        """frido.py:823-891: per-scale 1/scale_factor (fused into the VQ kernel) + first-stage decode."""
+        """frido.py:823-891: per-scale 1/scale_factor (fused into the VQ kernel) + first-stage decode.  With split_input_params set
+        and its patch_distributed_vq true (:840-877): the latent is unfolded (1/scale_factor is per pixel, so it stays in the VQ kernel of
+        the crops), all crops are decoded as one batch and folded at vqf x the resolution; to_uint8 converts in the fold kernel."""
         assert not predict_cids
         embed = self.first_stage_model.embed_dim
         if not self.adopted_scale_factor:
@@ -681,12 +710,36 @@ class FridoDiffusion(_Base):
         else:
             sfs = self.scale_factor.detach().float().cpu().numpy()
             inv = [float(np.float32(1.0) / np.float32(v)) for v in sfs]
+        from . import patching
+        patch = patching.params_of(self)
+        if patch is not None and patch["patch_distributed_vq"]:
+            if return_code or force_codes is not None:
+                raise patching.refuse("return_code / force_codes (the reference's patch-wise decode returns the image only)")
+            fs = self.first_stage_model
+            geo = patching.geometry(patch, z_in.shape[2], z_in.shape[3], patching.DECODE, z_in.device)
+            if not z_in.is_cuda:
+                _no_cpu("FridoDiffusion.decode_first_stage", z_in.device)
+            from . import autoplanes
+            return autoplanes.run(fs, lambda _n: fs.runtime().decode_patches(z_in, geo, inv_scale=inv, to_uint8=to_uint8),
+                                  "FridoDiffusion.decode_first_stage")
         return self.first_stage_model.decode(z_in, return_code=return_code, inv_scale=inv, to_uint8=to_uint8,
                                              force_codes=force_codes)
 
     @torch.no_grad()
     def encode_first_stage(self, x):
-        """frido.py:962-1005 (no split_input_params; the reference's duplicated encode call is not repeated)."""
+        """frido.py:962-1005 (the reference's duplicated encode call is not repeated).  With split_input_params set and its
+        patch_distributed_vq true (:963-993): image crops are encoded as one batch and folded at 1 / vqf of the resolution; the image size is
+        recorded in split_input_params['original_image_size'] like :968."""
+        from . import patching
+        patch = patching.params_of(self)
+        if patch is not None and patch["patch_distributed_vq"]:
+            patch["original_image_size"] = x.shape[-2:]
+            fs = self.first_stage_model
+            geo = patching.geometry(patch, x.shape[2], x.shape[3], patching.ENCODE, x.device)
+            if not x.is_cuda:
+                _no_cpu("FridoDiffusion.encode_first_stage", x.device)
+            from . import autoplanes
+            return autoplanes.run(fs, lambda _n: fs.runtime().encode_patches(x, geo), "FridoDiffusion.encode_first_stage")
         return self.first_stage_model.encode(x)
 
     @torch.no_grad()
@@ -774,6 +827,9 @@ class FridoDiffusion(_Base):
         return mean, self._extract("posterior_variance", t, x_t), self._extract("posterior_log_variance_clipped", t, x_t)
 
     def _anc_refuse(self, cond=None, quantize_denoised=False, return_codebook_ids=False, mask=None, x0=None, loop=False):
+        if hasattr(self, "split_input_params"):
+            from .patching import refuse
+            raise refuse("ancestral sampling (p_sample / p_mean_variance / p_sample_loop / progressive_denoising)")
         if quantize_denoised:
             raise NotImplementedError("quantize_denoised: `first_stage_model.quantize` does not exist on the MS-VQGAN (the reference raises an "
                                       "AttributeError at frido.py:1256)")

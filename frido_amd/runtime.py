@@ -129,8 +129,61 @@ def ancestral_step(builder, x, eps, rows, coef, start, *, noise=None, temperatur
         return nchw(xo), nchw(p0)
 
 
+def _relayout(builder, st, src, dst, B, HW, Cn, to_nchw):
+    _run1(builder, "FRIDO_OP_RELAYOUT", st, src=src.data_ptr(), dst=dst.data_ptr(), B=B, HW=HW, Csrc=Cn, c0=0, Cuse=Cn, Cdst=Cn, d0=0,
+          to_nchw=to_nchw)
+
+
+@torch.no_grad()
+def patch_unfold(builder, geo, x):
+    """x (B, C, H, W) f32 NCHW on the GPU -> its crops (B * L, C, kh, kw) NCHW (patching.PatchGeometry `geo`; crop l of sample b at
+    b * L + l): FRIDO_OP_RELAYOUT to NHWC, frido_unfold, FRIDO_OP_RELAYOUT back."""
+    from .patching import launch_unfold
+    B, Cn, H, W = x.shape
+    _, _, kh, kw, _, _ = geo.src
+    assert (H, W) == geo.src[:2]
+    dev, Bc = x.device, B * geo.L
+    with _lib.use_planes(builder.planes):
+        st = current_stream_ptr(dev)
+        x = x.contiguous()
+        xs = torch.empty(B, H * W, Cn, dtype=torch.float32, device=dev)
+        cs = torch.empty(Bc, kh * kw, Cn, dtype=torch.float32, device=dev)
+        out = torch.empty(Bc, Cn, kh, kw, dtype=torch.float32, device=dev)
+        _relayout(builder, st, x, xs, B, H * W, Cn, 0)
+        launch_unfold(geo.unfold_desc(xs.data_ptr(), cs.data_ptr(), B, Cn), st)
+        _relayout(builder, st, cs, out, Bc, kh * kw, Cn, 1)
+    return out
+
+
+@torch.no_grad()
+def patch_fold(builder, geo, o, B):
+    """o (B * L, C, kh', kw') f32 NCHW crops -> the weighted, normalised recombination (B, C, H', W') NCHW (the fold side of `geo`)."""
+    from .patching import launch_fold
+    Bc, Cn = o.shape[:2]
+    H, W, kh, kw, _, _ = geo.out
+    assert Bc == B * geo.L and tuple(o.shape[2:]) == (kh, kw), (tuple(o.shape), B, geo.L, kh, kw)
+    dev = o.device
+    with _lib.use_planes(builder.planes):
+        st = current_stream_ptr(dev)
+        o = o.contiguous().float()
+        cs = torch.empty(Bc, kh * kw, Cn, dtype=torch.float32, device=dev)
+        fs = torch.empty(B, H * W, Cn, dtype=torch.float32, device=dev)
+        out = torch.empty(B, Cn, H, W, dtype=torch.float32, device=dev)
+        _relayout(builder, st, o, cs, Bc, kh * kw, Cn, 0)
+        launch_fold(geo.fold_desc(cs.data_ptr(), fs.data_ptr(), B, Cn), st)
+        _relayout(builder, st, fs, out, B, H * W, Cn, 1)
+    return out
+
+
 class SamplerEngine:
-    """One instance per (denoiser weights, B, latent shape, context length, S, eta, cfg on/off, kind)."""
+    """One instance per (denoiser weights, B, latent shape, context length, S, eta, cfg on/off, kind, patch geometry).
+
+    patch (a split_input_params dict; DDIM / PLMS only): the patch-wise mode of frido.py:1076-1152.  The state x, pred_x0, the PLMS eps
+    ring, the stage hand-off and the update kernel stay on the FULL latent; the stage plans are built for the B * L crops (kh x kw) and
+    read a crop buffer, and every model evaluation is frido_unfold(x -> crops) -> step program -> frido_fold(crop eps -> full eps), all
+    inside the captured step body (patching.PatchProg).  A stage's `pre` program reads the crop buffer too (the SPADE maps come from the
+    frozen channels), so an unfold precedes it.  Memory: everything per-sample in the plans -- activations, the SPADE maps and the
+    cross-attention K / V^T caches (B * L * xrep rows) -- is L times the whole-latent engine's at the crop size."""
 
     def __init__(self, builder: Builder, cfg, **kw):
         self.planes = builder.planes
@@ -138,7 +191,7 @@ class SamplerEngine:
             self._init(builder, cfg, **kw)
 
     def _init(self, builder: Builder, cfg, *, B, C, H, W, nctx, S, eta, kind, alphas_cumprod, embed_dim, cfg_scale=1.0,
-              use_graph=True, num_stage=None, temperature=1.0, posterior=None, clip=False):
+              use_graph=True, num_stage=None, temperature=1.0, posterior=None, clip=False, patch=None):
         self.b, self.cfg = builder, cfg
         self.dev = builder.device
         self.B, self.C, self.H, self.W, self.nctx = B, C, H, W, nctx
@@ -171,13 +224,25 @@ class SamplerEngine:
                                       "use_split_head=True (every shipped Frido config)")
         self.x = torch.zeros(B, H * W, C, dtype=torch.float32, device=self.dev)
         self.pred_x0 = torch.zeros_like(self.x)
+        self.geo = None
+        self.Bm, (Hm, Wm), x_model = B, (H, W), self.x      # what the stage plans see: the latent, or (patch mode) its B * L crops
+        if patch is not None:
+            from . import patching
+            assert kind != "ddpm", "the ancestral loop has no patch-wise mode"
+            self.geo = patching.geometry(patch, H, W, patching.MODEL, self.dev)
+            self.Bm, (Hm, Wm) = B * self.geo.L, self.geo.src[2:4]
+            self.x_crops = x_model = torch.zeros(self.Bm, Hm * Wm, C, dtype=torch.float32, device=self.dev)
+            self.unfold_x = self.geo.unfold_desc(self.x.data_ptr(), self.x_crops.data_ptr(), B, C)
+            self.eps_full = []      # per stage: the folded eps [xrep][B][H * W][nch] the update kernel reads
         self.stages = []
         with self.b.persist_scope() as owned:       # this engine owns its plans' persistent buffers: evicting it frees them
             for s in range(self.num_stage):
-                plan = UNetStagePlan(self.b, cfg, B=B, H=H, W=W, nctx=nctx, stage=s, x_state=self.x, temb_rows=self.n_steps,
+                plan = UNetStagePlan(self.b, cfg, B=self.Bm, H=Hm, W=Wm, nctx=nctx, stage=s, x_state=x_model, temb_rows=self.n_steps,
                                      per_sample_t=False, step_ptr=self.step.data_ptr(), xrep=self.xrep,
                                      step_bx_ptr=self.step_bx.data_ptr() if self.labels else None)
                 self.stages.append(plan)
+                if self.geo is not None:
+                    self.eps_full.append(torch.zeros(self.xrep * B * H * W, plan.nch, dtype=torch.float32, device=self.dev))
         self._persist = owned
         self.graphs = {}
         self.noise_buf = None
@@ -206,7 +271,37 @@ class SamplerEngine:
         """Advance the device step counter (and, for a class-conditional denoiser, the per-sample table counter by delta * Bx)."""
         prog.emit("FRIDO_OP_STEP_ADD", step=self.step.data_ptr(), delta=delta)
         if self.labels:
-            prog.emit("FRIDO_OP_STEP_ADD", step=self.step_bx.data_ptr(), delta=delta * self.B * self.xrep)
+            prog.emit("FRIDO_OP_STEP_ADD", step=self.step_bx.data_ptr(), delta=delta * self.Bm * self.xrep)
+
+    def _prog(self):
+        """An empty program for a step body: in patch mode one whose op list may hold the unfold / fold launches."""
+        if self.geo is not None:
+            from .patching import PatchProg
+            return PatchProg(self.dev, self.b.nsplit)
+        from .engine import Prog
+        return Prog(self.dev, self.b.nsplit)
+
+    def _eval_ops(self, s):
+        """The ops of ONE model evaluation at stage s, leaving eps where _eps_ptr(s) points."""
+        plan = self.stages[s]
+        if self.geo is None:
+            return list(plan.step.ops)
+        from .patching import FOLD, UNFOLD
+        fold = self.geo.fold_desc(plan.eps.data_ptr(), self.eps_full[s].data_ptr(), self.xrep * self.B, plan.nch)
+        return [(UNFOLD, self.unfold_x)] + list(plan.step.ops) + [(FOLD, fold)]
+
+    def _eps_ptr(self, s):
+        return (self.eps_full[s] if self.geo is not None else self.stages[s].eps).data_ptr()
+
+    def _run_pre(self, plan, sp):
+        if self.geo is not None:
+            from .patching import launch_unfold
+            launch_unfold(self.unfold_x, sp)
+        plan.pre.run(sp)
+
+    def _per_crop(self, t):
+        """A per-sample input of the model ([xrep * B, ...]) repeated for its L crops (crop l of sample b is entry b * L + l)."""
+        return t.repeat_interleave(self.geo.L, dim=0) if self.geo is not None and t is not None else t
 
     def _sampler_op(self, s, *, noise_ptr, noise_C, seed, sample0, write_x=1, x_out=None, eps_out=None, hist=(),
                     row_offset=0, hist_mode=0, no_cfg=False):
@@ -215,7 +310,7 @@ class SamplerEngine:
         nch = self.embed[s]
         BHW = self.B * self.H * self.W
         kw = dict(x=self.x.data_ptr(), B=self.B, HW=self.H * self.W, Cx=self.C, start=start, nch=nch,
-                  eps_cond=plan.eps.data_ptr(), cfg_scale=self.cfg_scale, coef=self.coef.data_ptr(),
+                  eps_cond=self._eps_ptr(s), cfg_scale=self.cfg_scale, coef=self.coef.data_ptr(),
                   step=self.step.data_ptr(), coef_row_offset=row_offset, temperature=self.temperature,
                   x_out=(x_out if x_out is not None else self.x.data_ptr()), pred_x0=self.pred_x0.data_ptr(),
                   write_x=write_x, seed=seed, sample0=sample0, rng_stream=s + 1, rng_dev=self.rng.data_ptr(),
@@ -223,7 +318,7 @@ class SamplerEngine:
         if hist_mode:
             kw.update(hist_ring=self.hist.data_ptr(), hist_stride=self.hist_stride, hist_mode=hist_mode)
         if self.xrep == 2 and not no_cfg:
-            kw["eps_uncond"] = plan.eps.data_ptr() + 4 * BHW * nch
+            kw["eps_uncond"] = self._eps_ptr(s) + 4 * BHW * nch
         if noise_ptr:
             kw.update(noise=noise_ptr, noise_stride=BHW * noise_C, noise_C=noise_C, noise_c0=start)
         if eps_out is not None:
@@ -265,6 +360,9 @@ class SamplerEngine:
                           model=model, cond=cond, uncond=uncond)
         if noise_dropout > 0. and noise == "philox":
             raise NotImplementedError("noise_dropout draws its keep mask from torch's generator: use noise='torch' (or a recorded tape)")
+        if score_corrector is not None and self.geo is not None:
+            from .patching import refuse
+            raise refuse("score_corrector")
         stream = self._stream_ptr()
         stream.wait_stream(torch.cuda.current_stream(self.dev))
         sp = stream.cuda_stream
@@ -304,14 +402,14 @@ class SamplerEngine:
                 plan = self.stages[s]
                 Cs = sum(self.embed[:s + 1])
                 if self.labels:
-                    plan.set_labels(ctx)
+                    plan.set_labels(self._per_crop(ctx))
                 elif ctx is not None:
-                    plan.set_context(ctx)
+                    plan.set_context(self._per_crop(ctx))
                 plan.set_timesteps(t_loop)
                 self.step.zero_()
                 if self.labels:
                     self.step_bx.zero_()
-                plan.pre.run(sp)
+                self._run_pre(plan, sp)
                 if self.kind == "ddim":
                     self._ddim_stage(s, sp, draw, seed, sample0, inter, log_every_t, callback, img_callback, Cs)
                 else:
@@ -369,8 +467,8 @@ class SamplerEngine:
             noise_ptr, noise_C = self._upload_noise(s, [draw((self.B, Cs, self.H, self.W)) for _ in range(n)])
             key = ("ddim_tape", s)
             if key not in self.graphs:
-                body = Prog(self.dev, self.b.nsplit)
-                body.ops = list(plan.step.ops)
+                body = self._prog()
+                body.ops = self._eval_ops(s)
                 body.emit("FRIDO_OP_SAMPLER_STEP", **self._sampler_op(s, noise_ptr=noise_ptr, noise_C=noise_C, seed=0, sample0=0))
                 self._step_add(body, 1)
                 body.keep = [plan]
@@ -381,8 +479,8 @@ class SamplerEngine:
             self.rng.copy_(torch.tensor([seed, sample0], dtype=torch.int64))
             key = ("ddim", s)
             if key not in self.graphs:
-                full = Prog(self.dev, self.b.nsplit)
-                full.ops = list(plan.step.ops)
+                full = self._prog()
+                full.ops = self._eval_ops(s)
                 full.emit("FRIDO_OP_SAMPLER_STEP", **self._sampler_op(s, noise_ptr=None, noise_C=0, seed=0, sample0=0))
                 self._step_add(full, 1)
                 full.keep = [plan]
@@ -397,8 +495,7 @@ class SamplerEngine:
         if K > 1 and n >= K and callback is None and img_callback is None:
             kkey = key + ("x%d" % K,)
             if kkey not in self.graphs:
-                from .engine import Prog
-                multi = Prog(self.dev, self.b.nsplit)
+                multi = self._prog()
                 multi.ops = list(g.keep[1].ops) * K          # (Graph.keep = (packed descriptor array, the Prog it was captured from))
                 multi.keep = [plan]
                 self.graphs[kkey] = multi.capture(sp)
@@ -516,14 +613,14 @@ class SamplerEngine:
         nbytes = self.x.numel() * 4
 
         def build(first):
-            p = Prog(self.dev, self.b.nsplit)
-            p.ops = list(plan.step.ops)
+            p = self._prog()
+            p.ops = self._eval_ops(s)
             if first:
                 p.emit("FRIDO_OP_COPY", src=self.x.data_ptr(), dst=self.x_save.data_ptr(), n=nbytes)
                 p.emit("FRIDO_OP_SAMPLER_STEP", **self._sampler_op(s, noise_ptr=None, noise_C=0, seed=0, sample0=0, hist_mode=1))
                 if n > 1:
                     self._step_add(p, 1)
-                p.ops += list(plan.step.ops)
+                p.ops += self._eval_ops(s)
                 if n > 1:
                     self._step_add(p, -1)
                 p.emit("FRIDO_OP_COPY", src=self.x_save.data_ptr(), dst=self.x.data_ptr(), n=nbytes)
@@ -774,3 +871,78 @@ class DecoderRuntime:
         x_in.copy_(x)            # plumbing: D2D copy into the plan's fixed input buffer
         plan.prog.run(st)
         return plan.out.clone()
+
+    # ---- patch-wise mode (FridoDiffusion.split_input_params with patch_distributed_vq, frido.py:840-877, 963-993) ----
+    @_lib.with_planes
+    def decode_patches(self, z, geo, inv_scale=None, to_uint8=False):
+        """z (B, Ctot, h, w) NCHW latent -> image (B, 3, h * vqf, w * vqf): the latent's crops (patching.PatchGeometry `geo`, DECODE mode) are
+        decoded as ONE batch of B * L by the decode plan (f32 NHWC crops out of its last conv) and folded at image resolution; with
+        to_uint8 the fold kernel writes the (B, H, W, 3) uint8 image through the last conv's two conversions."""
+        from .patching import launch_fold, launch_unfold
+        B, Ct, h, w = z.shape
+        _, _, kh, kw, _, _ = geo.src
+        H, W, kho, kwo, _, _ = geo.out
+        embed = self.cfg["embed_dim"]
+        inv = tuple(float(v) for v in (inv_scale if inv_scale is not None else [1.0] * len(embed)))
+        u8 = self.U8_MODES[to_uint8]
+        Bc = B * geo.L
+        key = (Bc, kh, kw, inv, False, 0)
+        st = current_stream_ptr(self.device)
+        if key not in self.plans:
+            z_state = torch.zeros(Bc, kh * kw, Ct, dtype=torch.float32, device=self.device)
+            self.plans[key] = (z_state, VQDecodePlan(self.b, self.cfg["ddconfig"], embed, self.cfg["n_embed"], B=Bc, h=kh, w=kw,
+                                                      z_state=z_state, inv_scale=inv, forced=False, u8_mode=0))
+        z_state, plan = self.plans[key]
+        if (plan.H, plan.W) != (kho, kwo):
+            raise ValueError(f"split_input_params['vqf'] = {kho // kh} does not match the first stage, which decodes {kh} x {kw} latents to "
+                             f"{plan.H} x {plan.W} images")
+        Co = plan.a.out_ch
+        zc = z.contiguous().float()
+        zs = torch.empty(B, h * w, Ct, dtype=torch.float32, device=self.device)
+        _relayout(self.b, st, zc, zs, B, h * w, Ct, 0)
+        launch_unfold(geo.unfold_desc(zs.data_ptr(), z_state.data_ptr(), B, Ct), st)
+        plan.prog.run(st)
+        if u8:
+            img = torch.empty(B, H, W, Co, dtype=torch.uint8, device=self.device)
+            launch_fold(geo.fold_desc(plan.out_nhwc.data_ptr(), None, B, Co, out_u8=img.data_ptr(), u8_mode=u8), st)
+            return img
+        fs = torch.empty(B, H * W, Co, dtype=torch.float32, device=self.device)
+        launch_fold(geo.fold_desc(plan.out_nhwc.data_ptr(), fs.data_ptr(), B, Co), st)
+        out = torch.empty(B, Co, H, W, dtype=torch.float32, device=self.device)
+        _relayout(self.b, st, fs, out, B, H * W, Co, 1)
+        return out
+
+    @_lib.with_planes
+    def encode_patches(self, x, geo):
+        """x (B, 3, H, W) NCHW image -> pre-quantisation latent (B, sum(embed), H / vqf, W / vqf): image crops (`geo`, ENCODE mode) encoded
+        as one batch, folded at latent resolution."""
+        from .patching import launch_fold, launch_unfold
+        B, Cin, H, W = x.shape
+        _, _, kh, kw, _, _ = geo.src
+        Ho, Wo, kho, kwo, _, _ = geo.out
+        embed = self.cfg["embed_dim"]
+        Bc = B * geo.L
+        key = ("enc", Bc, kh, kw, tuple([1.0] * len(embed)))
+        st = current_stream_ptr(self.device)
+        if key not in self.plans:
+            x_in = torch.zeros(Bc, Cin, kh, kw, dtype=torch.float32, device=self.device)
+            self.plans[key] = (x_in, VQEncodePlan(self.b, self.cfg, B=Bc, H=kh, W=kw, x_in=x_in, scale=key[4]))
+        x_in, plan = self.plans[key]
+        Ce = plan.out.shape[1]
+        if tuple(plan.out.shape[2:]) != (kho, kwo):
+            raise ValueError(f"split_input_params['vqf'] = {kh // kho} does not match the first stage, which encodes {kh} x {kw} images to "
+                             f"{tuple(plan.out.shape[2:])} latents")
+        xc = x.contiguous().float()
+        xs = torch.empty(B, H * W, Cin, dtype=torch.float32, device=self.device)
+        cs = torch.empty(Bc, kh * kw, Cin, dtype=torch.float32, device=self.device)
+        _relayout(self.b, st, xc, xs, B, H * W, Cin, 0)
+        launch_unfold(geo.unfold_desc(xs.data_ptr(), cs.data_ptr(), B, Cin), st)
+        _relayout(self.b, st, cs, x_in, Bc, kh * kw, Cin, 1)
+        plan.prog.run(st)
+        os_ = torch.empty(Bc, kho * kwo, Ce, dtype=torch.float32, device=self.device)
+        fs = torch.empty(B, Ho * Wo, Ce, dtype=torch.float32, device=self.device)
+        out = torch.empty(B, Ce, Ho, Wo, dtype=torch.float32, device=self.device)
+        _relayout(self.b, st, plan.out, os_, Bc, kho * kwo, Ce, 0)
+        launch_fold(geo.fold_desc(os_.data_ptr(), fs.data_ptr(), B, Ce), st)
+        _relayout(self.b, st, fs, out, B, Ho * Wo, Ce, 1)
+        return out

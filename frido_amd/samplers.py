@@ -79,16 +79,19 @@ class _SamplerBase:
         self.ddim_sqrt_one_minus_alphas = np.sqrt((np.float32(1.0) - al).astype(np.float32))
         self.alphas_cumprod = ac
 
-    def _engine(self, B, shape, nctx, S, eta, scale, num_stage, temperature, replica=0):
+    def _engine(self, B, shape, nctx, S, eta, scale, num_stage, temperature, replica=0, patch=None):
         from .runtime import SamplerEngine
         unet = self.model.model.diffusion_model
         rt = unet.runtime()
         C, H, W = shape
         key = (self.KIND, B, C, H, W, nctx, S, float(eta), scale != 1.0, num_stage, float(temperature), replica)
+        if patch is not None:      # patch-wise mode (model.split_input_params): plans, buffers and graphs of its own
+            from .patching import geometry_key
+            key += (geometry_key(patch),)
         eng = cached_engine(rt, key, lambda: SamplerEngine(
             rt.builder_for(replica), unet.cfg, B=B, C=C, H=H, W=W, nctx=nctx if isinstance(nctx, int) else 0, S=S, eta=eta, kind=self.KIND,
             alphas_cumprod=self.model.alphas_cumprod.detach().float().cpu().numpy(), embed_dim=self.model.embed_dim_list, cfg_scale=scale,
-            num_stage=num_stage, temperature=temperature))
+            num_stage=num_stage, temperature=temperature, patch=patch))
         eng.cfg_scale = float(scale)      # read from a device scalar by the captured step bodies: one graph, any scale
         return eng
 
@@ -107,6 +110,15 @@ class _SamplerBase:
         if quantize_x0:
             raise NotImplementedError("quantize_x0: the reference calls exit() on this option (ddim.py:251-253)")
         unet = getattr(getattr(self.model, "model", None), "diffusion_model", None)
+        # patch-wise mode (frido.py:1076-1152): the samplers inherit it from apply_model; looked up on every call, like the reference's hasattr
+        from . import patching
+        patch = patching.params_of(self.model)
+        if patch is not None:
+            if score_corrector is not None:
+                raise patching.refuse("score_corrector")
+            patching.check_conditioning(self.model, conditioning)
+            patching.check_conditioning(self.model, unconditional_conditioning)
+            patching.geometry(patch, shape[1], shape[2], patching.MODEL, None)      # the geometry's own refusals, before anything is planned
         # engine-cache key: context length, or which conditioning mode the plans were built for
         mode = check_conditioning(unet, conditioning, batch_size)
         if conditioning is None:
@@ -129,7 +141,7 @@ class _SamplerBase:
             # the engine is looked up per attempt: a repeated run (autoplanes: the default plane format saturated) belongs to the
             # denoiser's NEW runtime on the bf16-pair build, with its own plans, buffers and graphs
             eng = self._engine(batch_size, tuple(shape), mode, S, eta, unconditional_guidance_scale, num_stage,
-                               temperature, replica)
+                               temperature, replica, patch)
             return eng.run(conditioning, unconditional_conditioning, x_T=x_T, noise=noise_src, seed=seed, sample0=sample0,
                            log_every_t=log_every_t, callback=callback, img_callback=img_callback, noise_dropout=noise_dropout,
                            score_corrector=score_corrector, corrector_kwargs=corrector_kwargs, model=self.model)

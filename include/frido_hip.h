@@ -428,6 +428,26 @@ typedef struct FridoFill { uint32_t* dst; int64_t n; uint32_t value; } FridoFill
  * captured into the hipGraph as parallel branches. */
 typedef struct FridoSync { int32_t from, to; } FridoSync;
 
+/* ---- patch-wise ("convolutional") mode: FridoDiffusion.split_input_params (frido/models/diffusion/frido.py:714-764, 1076-1152) ----
+ * Not op kinds: exported launchers with descriptors of their own (frido_unfold / frido_fold below); a step body that contains them
+ * is captured between frido_capture_begin and frido_capture_end.
+ *
+ * Crops of an NHWC f32 map src[B][H][W][C]: dst[Bc][kh][kw][C], Bc = B * L, L = Ly * Lx, Ly = (H - kh) / sy + 1, Lx = (W - kw) / sx + 1
+ * (both divisions exact).  Crop l = ly * Lx + lx starts at (ly * sy, lx * sx) -- nn.Unfold's order.
+ * BATCH LAYOUT (shared with FridoFold): crop l of sample b is entry  bc = b * L + l  -- a sample's crops are adjacent, so a tensor of
+ * [r][b] groups (classifier-free guidance: r = cond / uncond) is ONE call with B = R * B.  The copy is exact. */
+typedef struct FridoUnfold { const float* src; float* dst; int32_t B, H, W, C, kh, kw, sy, sx; } FridoUnfold;
+
+/* The inverse, in gather form (one thread per output element or 4-channel vector, no atomics: the same bits on every launch):
+ *   out[b][y][x][c] = ( sum over the crops l that cover (y, x), ascending l, of
+ *                       crops[b * L + l][y - y0_l][x - x0_l][c] * wt[((y - y0_l) * kw + (x - x0_l)) * L + l] ) / norm[y * W + x]
+ * every product and sum rounded to fp32 on its own (no contraction), a true division.  wt [kh * kw][L] and norm [H * W] are the
+ * reference's `weighting` and `normalization` tensors (get_weighting / fold(weighting)), computed by the host once per geometry.
+ * C is the channel count of the crop tensor.  out (f32) and out_u8 are both optional, at least one is set: out_u8 [B][H][W][C] receives
+ * the folded value through FridoGemm.out_u8's conversions, u8_mode 1 (custom_to_np) or 2 (custom_to_pil). */
+typedef struct FridoFold { const float* crops; float* out; const float* wt; const float* norm; uint8_t* out_u8;
+                           int32_t B, H, W, C, kh, kw, sy, sx, u8_mode; } FridoFold;
+
 enum FridoOpKind {
     FRIDO_OP_GEMM = 1, FRIDO_OP_GN_STATS, FRIDO_OP_GN_APPLY, FRIDO_OP_LAYERNORM, FRIDO_OP_SOFTMAX,
     FRIDO_OP_GEGLU, FRIDO_OP_PACK, FRIDO_OP_RELAYOUT, FRIDO_OP_VQ, FRIDO_OP_SAMPLER_STEP,
@@ -503,6 +523,16 @@ int frido_run_timed(const FridoOp* ops, int32_t n, frido_stream_t s, float* ms);
 int frido_graph_capture(const FridoOp* ops, int32_t n, frido_stream_t s, void** out);
 int frido_graph_launch(void* graph, frido_stream_t s);
 int frido_graph_destroy(void* graph);
+/* The two halves of frido_graph_capture (= begin + frido_run + end): whatever the caller launches on `s` in between -- frido_run
+ * programs, frido_unfold / frido_fold -- becomes ONE graph, instantiated by frido_capture_end (*graph: the handle frido_graph_launch /
+ * frido_graph_destroy take).  frido_capture_end must be called after a successful begin even when a launch in between failed (it ends
+ * the capture); it then returns an error and no graph. */
+int frido_capture_begin(frido_stream_t s);
+int frido_capture_end(frido_stream_t s, void** graph);
+
+/* ---- patch-wise mode (descriptors above) ---- */
+int frido_unfold(const FridoUnfold* d, frido_stream_t s);
+int frido_fold(const FridoFold* d, frido_stream_t s);
 
 /* ---- timing on the launch stream (HIP events) ---- */
 int frido_event_create(void** ev);
