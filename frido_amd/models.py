@@ -524,7 +524,7 @@ class DiffusionWrapper(_Base):
 
 
 class FridoDiffusion(_Base):
-    """frido.py:45-124 (DDPM.__init__) + 478-555 (FridoDiffusion.__init__), inference subset."""
+    """frido.py:45-124 (DDPM.__init__) + 478-555 (FridoDiffusion.__init__): sampling, and the objective without a backward pass."""
 
     def __init__(self, first_stage_config, cond_stage_config, num_timesteps_cond=None, cond_stage_key="image",
                  cond_stage_trainable=False, concat_mode=True, cond_stage_forward=None, conditioning_key=None,
@@ -566,10 +566,18 @@ class FridoDiffusion(_Base):
         if use_ema:
             self.model_ema = LitEma(self.model)
         self.v_posterior = v_posterior
+        # the objective's options (frido.py:105-124, 515-520)
+        self.loss_type, self.noise_mix_ratio, self.stage_loss_ratio = loss_type, noise_mix_ratio, list(stage_loss_ratio)
+        self.l_simple_weight, self.original_elbo_weight, self.learn_logvar = l_simple_weight, original_elbo_weight, learn_logvar
         if monitor is not None:
             self.monitor = monitor
         self.register_schedule(given_betas=given_betas, beta_schedule=beta_schedule, timesteps=timesteps,
                                linear_start=linear_start, linear_end=linear_end, cosine_s=cosine_s)
+        # frido.py:120-123: a plain tensor (no state_dict key) unless it is learned
+        self.logvar = torch.full(fill_value=logvar_init, size=(self.num_timesteps,))
+        if learn_logvar:
+            self.logvar = nn.Parameter(self.logvar, requires_grad=True)
+        self.shorten_cond_schedule = self.num_timesteps_cond > 1
         self.concat_mode, self.cond_stage_trainable, self.cond_stage_key = concat_mode, cond_stage_trainable, cond_stage_key
         self.cond_stage_forward = cond_stage_forward
         self.use_prob = use_prob
@@ -595,6 +603,12 @@ class FridoDiffusion(_Base):
         for k, v in schedules.ddpm_tables(betas, v_posterior=self.v_posterior).items():
             self.register_buffer(k, torch.from_numpy(v))
         self._anc_tabs = {}      # device coefficient tables of the ancestral update, per (device, clip, with noise)
+        # frido.py:169-178 (eps parameterization), float32 torch arithmetic on the registered buffers like the reference's
+        alphas = torch.tensor(1. - np.asarray(betas, dtype=np.float64), dtype=torch.float32)
+        lvlb_weights = self.betas ** 2 / (2 * self.posterior_variance * alphas * (1 - self.alphas_cumprod))
+        lvlb_weights[0] = lvlb_weights[1]
+        self.register_buffer("lvlb_weights", lvlb_weights, persistent=False)
+        assert not torch.isnan(self.lvlb_weights).all()
 
     def init_from_ckpt(self, path, ignore_keys=list(), only_model=False):
         sd = torch.load(path, map_location="cpu")
@@ -624,12 +638,23 @@ class FridoDiffusion(_Base):
                 self.cond_stage_model.eval()
 
     @contextlib.contextmanager
-    def ema_scope(self, context=None):
-        """frido.py:181-194: sample with the EMA weights, then restore."""
+    def ema_scope(self, context=None, *, keep_runtimes=False):
+        """frido.py:181-194: sample with the EMA weights, then restore.  Both swaps drop the denoiser's compiled runtime (plans, engines,
+        graphs).  keep_runtimes (validation_step, which enters this scope once per batch): keep one runtime per weight set instead --
+        the raw weights' is put back as it was (restore() writes back the very bits it was compiled from), the EMA weights' is reused
+        by the next such scope as long as no tensor of the EMA shadow was written since (their version counters).  Costs a second set
+        of packed weights and engines on the device."""
+        unet = self.model.diffusion_model
         if self.use_ema:
             self.model_ema.store(self.model.parameters())
             self.model_ema.copy_to(self.model)
-            self.model.diffusion_model.invalidate()
+            if keep_runtimes:
+                raw = (unet._rt, unet._rt_key)
+                shadow = tuple(b._version for b in self.model_ema.buffers())
+                kept = self.__dict__.get("_ema_rt")
+                unet._rt, unet._rt_key = kept[1:] if kept is not None and kept[0] == shadow else (None, None)
+            else:
+                unet.invalidate()
             if context is not None:
                 print(f"{context}: Switched to EMA weights")
         try:
@@ -637,7 +662,11 @@ class FridoDiffusion(_Base):
         finally:
             if self.use_ema:
                 self.model_ema.restore(self.model.parameters())
-                self.model.diffusion_model.invalidate()
+                if keep_runtimes:
+                    self.__dict__["_ema_rt"] = (shadow, unet._rt, unet._rt_key)
+                    unet._rt, unet._rt_key = raw
+                else:
+                    unet.invalidate()
                 if context is not None:
                     print(f"{context}: Restored training weights")
 
@@ -1007,8 +1036,179 @@ class FridoDiffusion(_Base):
             return DDIMSampler(self).sample(ddim_steps, batch_size, shape, cond, num_stage=num_stage, verbose=False, **kwargs)
         return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, **kwargs)
 
-    def forward(self, *a, **k):
-        raise FridoHipError("training (FridoDiffusion.forward / p_losses) is outside the inference hot path")
+    # ---- the objective (frido.py:196-228, 322-345, 382-419, 1007-1050, 1162-1224) -----------------------------------------------------
+    # Evaluating it needs no gradient: it is what test_step / validation_step do.  q_sample, the denoiser and the loss of every stage run
+    # as ONE captured graph (frido_amd/objective.py LossEngine); the helpers below are plain tensor arithmetic like q_sample.
+    def get_loss(self, pred, target, mean=True):
+        """frido.py:322-336."""
+        if self.loss_type == "l1":
+            loss = (target - pred).abs()
+            return loss.mean() if mean else loss
+        if self.loss_type == "l2":
+            return torch.nn.functional.mse_loss(target, pred, reduction="mean" if mean else "none")
+        raise NotImplementedError(f"unknown loss type '{self.loss_type}'")
+
+    def q_mean_variance(self, x_start, t):
+        """frido.py:196-207: mean, variance and log variance of q(x_t | x_0), each broadcast against x_start."""
+        mean = self._extract("sqrt_alphas_cumprod", t, x_start) * x_start
+        shape = (x_start.shape[0],) + (1,) * (x_start.dim() - 1)
+        t = torch.as_tensor(t, device=x_start.device, dtype=torch.long)
+        variance = (1.0 - self.alphas_cumprod).to(x_start.device).gather(-1, t).reshape(shape)
+        return mean, variance, self._extract("log_one_minus_alphas_cumprod", t, x_start)
+
+    def _predict_eps_from_xstart(self, x_t, t, pred_xstart):
+        """frido.py:1162-1164."""
+        return (self._extract("sqrt_recip_alphas_cumprod", t, x_t) * x_t - pred_xstart) / self._extract("sqrt_recipm1_alphas_cumprod", t, x_t)
+
+    def _prior_bpd(self, x_start):
+        """frido.py:1166-1178: KL(q(x_T | x_0) || N(0, I)) per sample in bits per dimension (normal_kl + mean_flat of the published
+        guided-diffusion losses, against a standard normal)."""
+        t = torch.tensor([self.num_timesteps - 1] * x_start.shape[0], device=x_start.device)
+        mean1, _, logvar1 = self.q_mean_variance(x_start, t)
+        logvar2 = torch.tensor(0.0).to(logvar1)
+        kl = 0.5 * (-1.0 + logvar2 - logvar1 + torch.exp(logvar1 - logvar2) + ((mean1 - 0.0) ** 2) * torch.exp(-logvar2))
+        return kl.mean(dim=list(range(1, kl.dim()))) / np.log(2.0)
+
+    def _objective_refuse(self, cond):
+        if hasattr(self, "split_input_params"):
+            from .patching import refuse
+            raise refuse("the objective (forward / p_losses / validation_step)")
+        if self.shorten_cond_schedule:
+            raise NotImplementedError("shorten_cond_schedule (num_timesteps_cond > 1, frido.py:1031-1033): the q_sample of the conditioning is not built")
+        if isinstance(cond, (dict, list)):
+            raise NotImplementedError("dict / list conditionings: pass the cross-attention conditioning tensor or the class labels")
+        if self.model.conditioning_key in ("concat", "hybrid"):
+            raise NotImplementedError(f"conditioning_key={self.model.conditioning_key!r}: the objective is built for 'crossattn', 'adm' and "
+                                      "unconditional denoisers")
+        if not self.use_split_head:
+            raise NotImplementedError("use_split_head=False: the objective compares the stage's own eps channels, which needs the split head "
+                                      "(every shipped Frido config)")
+
+    def _objective(self, x_start, cond, t, noise, seed, sample0, stages=None):
+        """Stage rows [num_stage][4] = {loss_simple, loss_gamma, loss_vlb, loss} and per-sample loss_simple [num_stage][B] of ONE engine call
+        (device tensors; `stages`: the stages that run and whose rows are valid, default all).
+        noise: "philox", or a list with one (B, C, H, W) tensor per stage (None for a stage that does not run).
+        The engine is cached per (B, latent shape, conditioning mode, T); the schedule tables and logvar are handed over on every call
+        and the objective's scalars key its graphs, so a changed schedule, weight or loss type is in force at the next call."""
+        from . import autoplanes, samplers
+        from .objective import LossEngine
+        unet = self.model.diffusion_model
+        if not x_start.is_cuda:
+            _no_cpu("FridoDiffusion.p_losses", x_start.device)
+        if cond is not None and not cond.is_cuda:
+            _no_cpu("FridoDiffusion.p_losses", cond.device)
+        if next(unet.parameters()).device.type != "cuda":
+            _no_cpu("FridoDiffusion.p_losses", next(unet.parameters()).device)
+        B, C, H, W = (int(v) for v in x_start.shape)
+        tl = torch.as_tensor(t).reshape(-1)
+        assert tl.shape[0] == B, "t: one timestep per sample"
+        if not tl.is_cuda:      # (a device t is not read back: the kernels clamp it to the tables)
+            assert bool(((tl >= 0) & (tl < self.num_timesteps)).all()), "t: one timestep in [0, num_timesteps) per sample"
+        mode = samplers.check_conditioning(unet, cond, B, name="cond")
+        assert len(self.stage_loss_ratio) == self.num_resulotion, "Incorrect number of stage_loss_ratio."
+        key = ("loss", B, C, H, W, mode, self.num_timesteps)
+        tables = (self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, self.lvlb_weights)
+        tape = None if isinstance(noise, str) else list(noise)
+
+        def go(_n):
+            rt = unet.runtime()
+            eng = samplers.cached_engine(rt, key, lambda: LossEngine(
+                rt.builder_for(0), unet.cfg, B=B, C=C, H=H, W=W, nctx=mode if isinstance(mode, int) else 0, embed_dim=self.embed_dim_list,
+                num_stage=self.num_resulotion, T=self.num_timesteps))
+            return eng.run(x_start, cond, tl, tables=tables, tape=tape, seed=seed, sample0=sample0, logvar=self.logvar, stages=stages,
+                           loss_type=self.loss_type, mix_tau=self.noise_mix_ratio, l_simple_weight=self.l_simple_weight,
+                           original_elbo_weight=self.original_elbo_weight)
+        return autoplanes.run(unet, go, "FridoDiffusion.p_losses")
+
+    def _loss_dict(self, row, stage):
+        """p_losses' dict of one stage row (frido.py:1188-1222), values as 0-dim device tensors."""
+        prefix = "train" if self.training else "val"
+        d = {f"{prefix}/loss_simple_stage{stage}": row[0]}
+        if self.learn_logvar:
+            d[f"{prefix}/loss_gamma"] = row[1]
+            d["logvar"] = self.logvar.data.mean()
+        d[f"{prefix}/loss_vlb_stage{stage}"] = row[2]
+        d[f"{prefix}/loss"] = row[3]
+        return row[3], d
+
+    @torch.no_grad()
+    def p_losses(self, x_start, cond, t, stage, noise=None, *, seed=0, sample0=0, return_per_sample=False):
+        """frido.py:1180-1224: (loss, loss_dict) of one stage -- only that stage's launches run (a graph of its own on the engine that
+        forward uses).  noise: None / "torch" draws randn_like(x_start) from the host generator (the reference's draw), a tensor is used
+        as it is, "philox" draws in the kernels keyed by (seed, sample0 + b, stage).
+        return_per_sample: also the per-sample loss_simple [B]."""
+        self._objective_refuse(cond)
+        stage = int(stage)
+        if isinstance(noise, str) and noise == "philox":
+            tape = "philox"
+        else:
+            n = torch.randn(tuple(x_start.shape)) if noise is None or isinstance(noise, str) else noise
+            tape = [n if s == stage else None for s in range(self.num_resulotion)]
+        assert 0 <= stage < self.num_resulotion, f"stage {stage}: the model has {self.num_resulotion}"
+        rows, per = self._objective(x_start, cond, t, tape, seed, sample0, stages=(stage,))
+        out = self._loss_dict(rows[stage], stage)
+        return out + (per[stage],) if return_per_sample else out
+
+    @torch.no_grad()
+    def forward(self, x, c, *args, t=None, noise=None, seed=0, sample0=0, **kwargs):
+        """frido.py:1026-1050: t = randint(0, T, (B,)) first (unless given), then per stage one randn_like(x) and p_losses; stage values are
+        combined with stage_loss_ratio -- including the reference's quirk that a key shared between stages ('{prefix}/loss', and under
+        learn_logvar 'loss_gamma' / 'logvar') accumulates the already-weighted values.  All stages run in ONE engine call.
+        noise: None / "torch" (host generator, draw for draw), "philox" (rng_stream = stage), or a tensor (the same noise for every stage,
+        the reference's `p_losses(..., noise=)` meaning)."""
+        if args or kwargs:
+            raise TypeError(f"FridoDiffusion.forward: unexpected arguments {args} {sorted(kwargs)} (p_losses takes noise= only)")
+        self._objective_refuse(c)
+        if t is None:
+            t = torch.randint(0, self.num_timesteps, (x.shape[0],)).long()
+        if self.model.conditioning_key is not None:
+            assert c is not None
+            if self.cond_stage_trainable:
+                c = self.get_learned_conditioning(c)
+        S = self.num_resulotion
+        assert len(self.stage_loss_ratio) == S, "Incorrect number of stage_loss_ratio."
+        if isinstance(noise, str) and noise == "philox":
+            tape = "philox"
+        elif noise is None or isinstance(noise, str):
+            tape = [torch.randn(tuple(x.shape)) for _ in range(S)]
+        else:
+            tape = [noise] * S
+        rows, _ = self._objective(x, c, t, tape, seed, sample0)
+        total_loss = torch.zeros((), device=x.device)
+        total_loss_dict = dict()
+        for s in range(S):
+            loss, loss_dict = self._loss_dict(rows[s], s)
+            total_loss = total_loss + loss * self.stage_loss_ratio[s]
+            for k, v in loss_dict.items():
+                total_loss_dict[k] = total_loss_dict[k] + v * self.stage_loss_ratio[s] if k in total_loss_dict else v * self.stage_loss_ratio[s]
+        return total_loss, total_loss_dict
+
+    def shared_step(self, batch, **kwargs):
+        """frido.py:1007-1009."""
+        x, c = self.get_input(batch, self.first_stage_key)
+        return self(x, c, **kwargs)
+
+    def training_step(self, batch, batch_idx):
+        raise FridoHipError("training_step: no backward pass exists on the HIP path (the objective is evaluated without gradients: "
+                            "forward / p_losses / validation_step / test_step)")
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx, **kwargs):
+        """frido.py:401-411: the raw weights' dict, then the EMA weights' with '_ema' key suffixes; both are logged and the merged dict is
+        returned.  The scope keeps one compiled runtime per weight set (ema_scope(keep_runtimes=True)), so from the second batch on
+        both passes replay their captured graphs."""
+        _, loss_dict_no_ema = self.shared_step(batch, **kwargs)
+        with self.ema_scope(keep_runtimes=True):
+            _, loss_dict_ema = self.shared_step(batch, **kwargs)
+            loss_dict_ema = {key + "_ema": loss_dict_ema[key] for key in loss_dict_ema}
+        self.log_dict(loss_dict_no_ema, prog_bar=False, logger=True, on_step=False, on_epoch=True)
+        self.log_dict(loss_dict_ema, prog_bar=False, logger=True, on_step=False, on_epoch=True)
+        return {**loss_dict_no_ema, **loss_dict_ema}
+
+    @torch.no_grad()
+    def test_step(self, batch, batch_idx, **kwargs):
+        """frido.py:413-417."""
+        return self.shared_step(batch, **kwargs)
 
 
 MSLatentDiffusion = FridoDiffusion   # stale alias `ldm.models.diffusion.msldm.MSLatentDiffusion` in two shipped configs

@@ -179,10 +179,11 @@ def geometry_key(params):
 
 # ---- a program whose op list may contain the two kernels ------------------------------------------------------------------------------
 UNFOLD, FOLD = "unfold", "fold"
+FOREIGN = {UNFOLD: "frido_unfold", FOLD: "frido_fold"}      # op tag -> exported launcher taking (descriptor, stream); frido_amd/objective.py adds its two
 
 
 class PatchProg(Prog):
-    """Prog whose `ops` may also hold (UNFOLD, FridoUnfold) / (FOLD, FridoFold) entries.  run(): the descriptor ops in between go
+    """Prog whose `ops` may also hold (UNFOLD, FridoUnfold) / (FOLD, FridoFold) entries -- any (tag, descriptor) of FOREIGN.  run(): the descriptor ops in between go
     through frido_run, segment by segment, in order on the stream; capture(): the same sequence between frido_capture_begin and
     frido_capture_end -- one graph, replayed with frido_graph_launch like any other."""
 
@@ -190,7 +191,7 @@ class PatchProg(Prog):
         if self._packed is None:
             segs, cur = [], []
             for op in self.ops:
-                if op[0] in (UNFOLD, FOLD):
+                if op[0] in FOREIGN:
                     if cur:
                         segs.append(("ops", _lib.pack_ops(cur), len(cur)))
                         cur = []
@@ -205,10 +206,9 @@ class PatchProg(Prog):
     def _launch_all(self, stream):
         L = _lib.lib()
         for kind, what, n in self.packed():
-            if kind == UNFOLD:
-                rc, name = L.frido_unfold(C.byref(what), stream), "frido_unfold"
-            elif kind == FOLD:
-                rc, name = L.frido_fold(C.byref(what), stream), "frido_fold"
+            if kind in FOREIGN:
+                name = FOREIGN[kind]
+                rc = getattr(L, name)(C.byref(what), stream)
             else:
                 rc, name = L.frido_run(C.addressof(what), n, stream), "frido_run"
             if rc != 0:

@@ -448,6 +448,39 @@ typedef struct FridoUnfold { const float* src; float* dst; int32_t B, H, W, C, k
 typedef struct FridoFold { const float* crops; float* out; const float* wt; const float* norm; uint8_t* out_u8;
                            int32_t B, H, W, C, kh, kw, sy, sx, u8_mode; } FridoFold;
 
+/* ---- the diffusion objective: FridoDiffusion.forward / p_losses (frido/models/diffusion/frido.py:1007-1050, 1180-1224) ----
+ * Not op kinds either: two exported launchers with descriptors of their own (frido_qsample / frido_diffusion_loss below), run eagerly or
+ * between frido_capture_begin and frido_capture_end.  Both take their noise as a tape [B][HW][Cx] (NHWC f32, the full latent) or, with
+ * noise == NULL, draw it: Philox4x32-10 in frido_randn's numbering -- 4-float groups over the flat sample [HW][Cx] (HW * Cx a multiple
+ * of 4), key (seed, sample0 + b, rng_stream); rng_dev, an optional device {seed, sample0}, overrides the two fields (graph replay).
+ * t is a device int64 [B]; a value outside [0, T) reads the nearest table row.
+ *
+ * q_sample as p_losses calls it (frido.py:302-318, 1184): x_noisy[B][HW][ch_end] from x0[B][HW][Cx], every product and sum rounded to
+ * fp32 on its own (no contraction):
+ *   channels [ch_start, ch_end): sqrt_ac[t_b] * x0 + sqrt_1mac[t_b] * n
+ *   channels [0, ch_start):      x0 when mix_tau == 0, else (1 - mix_tau) * x0 + mix_tau * n, both factors Python doubles cast to fp32
+ * Channels from ch_end on (the reference fills them with noise) are not written: x_noisy is the stage plan's input and the split head
+ * never reads them (pyunet.py:899-907).  Cx and ch_end multiples of 4: one pass of 16-byte accesses (x0, x_noisy, noise 16-byte aligned). */
+typedef struct FridoQSample { const float* x0; float* x_noisy; const int64_t* t; const float* sqrt_ac; const float* sqrt_1mac;
+                              const float* noise; const int64_t* rng_dev; uint64_t seed; int64_t sample0; double mix_tau;
+                              int32_t B, HW, Cx, ch_start, ch_end, T, rng_stream; } FridoQSample;
+
+/* The loss of one stage (frido.py:1196-1222): pred[B][HW][nch] is the denoiser's eps, the target channels [ch_start, ch_start + nch) of
+ * the SAME noise (the tape, or Philox regenerated from the key frido_qsample used).  Element loss in fp32: |target - pred| (loss_type 0,
+ * 'l1') or (target - pred)^2 (1, 'l2'); the sum over a sample's HW * nch elements in f64, in a fixed order that depends on neither B nor
+ * the sample's position in the batch, no atomics; per_sample[b] = the mean, stored as f32 (loss_simple).  With `out` set (then t, logvar[T]
+ * and lvlb_weights[T] are required) a second launch on the same stream finishes the stage row, f64 sums over the batch stored as f32:
+ *   out[0] = mean_b ls_b                               ('loss_simple')
+ *   out[1] = mean_b (ls_b / exp(logvar[t_b]) + logvar[t_b])   ('loss_gamma')
+ *   out[2] = mean_b (lvlb_weights[t_b] * ls_b)         ('loss_vlb')
+ *   out[3] = l_simple_weight * out[1] + original_elbo_weight * out[2]   ('loss')
+ * Cx, ch_start and nch multiples of 4: 16-byte accesses (pred and noise 16-byte aligned). */
+typedef struct FridoDiffusionLoss { const float* pred; const int64_t* t; const float* noise; const int64_t* rng_dev;
+                                    const float* logvar; const float* lvlb_weights; float* per_sample; float* out;
+                                    uint64_t seed; int64_t sample0;
+                                    int32_t B, HW, Cx, ch_start, nch, T, rng_stream, loss_type;
+                                    float l_simple_weight, original_elbo_weight; } FridoDiffusionLoss;
+
 enum FridoOpKind {
     FRIDO_OP_GEMM = 1, FRIDO_OP_GN_STATS, FRIDO_OP_GN_APPLY, FRIDO_OP_LAYERNORM, FRIDO_OP_SOFTMAX,
     FRIDO_OP_GEGLU, FRIDO_OP_PACK, FRIDO_OP_RELAYOUT, FRIDO_OP_VQ, FRIDO_OP_SAMPLER_STEP,
@@ -533,6 +566,10 @@ int frido_capture_end(frido_stream_t s, void** graph);
 /* ---- patch-wise mode (descriptors above) ---- */
 int frido_unfold(const FridoUnfold* d, frido_stream_t s);
 int frido_fold(const FridoFold* d, frido_stream_t s);
+
+/* ---- the diffusion objective (descriptors above); bad arguments return FRIDO_EINVAL before any device is touched ---- */
+int frido_qsample(const FridoQSample* d, frido_stream_t s);
+int frido_diffusion_loss(const FridoDiffusionLoss* d, frido_stream_t s);
 
 /* ---- timing on the launch stream (HIP events) ---- */
 int frido_event_create(void** ev);

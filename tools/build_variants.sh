@@ -12,7 +12,7 @@ while [ $# -ge 2 ]; do
     rest="frido_amd/csrc/norm.o frido_amd/csrc/misc.o frido_amd/csrc/attn.o frido_amd/csrc/flash.o frido_amd/csrc/runtime.o"
     if [ "$name" = head ]; then      # EVERY source as committed at HEAD
       src=/tmp/variants_head; rm -rf $src; mkdir -p $src
-      for f in igemm.hip convgn.hip igemm_shared.h common.h norm.hip misc.hip attn.hip flash.hip runtime.hip; do git show HEAD:frido_amd/csrc/$f > $src/$f; done
+      for f in igemm.hip convgn.hip igemm_shared.h common.h philox.h norm.hip misc.hip attn.hip flash.hip runtime.hip; do git show HEAD:frido_amd/csrc/$f > $src/$f; done
       rest=""
       for f in norm misc attn flash runtime; do /opt/rocm/bin/hipcc $FL -I$src -c $src/$f.hip -o tools/ablate/${f}_head.o; rest="$rest tools/ablate/${f}_head.o"; done
     fi
