@@ -185,7 +185,7 @@ class PyUNetModel(_Versioned, nn.Module):
 UNetModel = PyUNetModel   # `ldm.modules.diffusionmodules.openaimodel.UNetModel` alias used by two shipped configs
 
 
-# ---- first stage (taming/models/msvqgan.py:16-96,320-399) ---------------------------------------------
+# ---- first stage (taming/models/msvqgan.py:16-96,320-399; the model of its own: 16-318) ---------------------------------------------
 class DummyLoss(nn.Module):   # taming/modules/losses/vqperceptual.py:12-14
     def __init__(self, *a, **k):
         super().__init__()
@@ -273,6 +273,187 @@ class VQModelInterface(_Versioned, _Base):
         assert len(self.channel_range) != 2, "channel_range slicing is not used by any shipped config"
         from . import autoplanes
         return autoplanes.run(self, lambda _n: self.runtime().encode(x, scale=scale), "VQModelInterface.encode")
+
+
+class MSFPNVQModel(_Versioned, _Base):
+    """taming/models/msvqgan.py:16-318: the MS-VQGAN as a model of its own -- what `main.py -t False` runs on configs/msvqgan/*.yaml.
+    Where VQModelInterface hands the diffusion model the PRE-quant latent, this class returns what the tokenizer itself computes: the
+    quantised multi-scale latent, the codes of every scale and the codebook loss (encode), an image from an already quantised latent
+    (decode), the reconstruction (forward) and the per-scale reconstructions (log_images).
+
+    CHANNEL ORDER: `quant` is [fine .. coarse] (the reference reverses its list before the concat, msvqgan.py:146), coarser scales
+    nearest-upsampled to the finest grid -- the OPPOSITE of VQModelInterface.encode's [coarse .. fine].
+    Same parameter / state_dict key set as the reference's class; no backward pass, no LPIPS / PatchGAN loss module."""
+
+    def __init__(self, edconfig, ddconfig, lossconfig, n_embed, embed_dim, fusion="concat", ckpt_path=None, ignore_keys=[],
+                 image_key="image", colorize_nlabels=None, monitor=None, remap=None, sane_index_shape=False, on_vit=[],
+                 use_aux_loss=False, unsample_type="nearest", quant_beta=0.25, legacy=True, init_normal=False, precision=None):
+        super().__init__()
+        edconfig, ddconfig = _plain(edconfig), _plain(ddconfig)
+        embed_dim, n_embed = list(embed_dim), list(n_embed)
+        if remap is not None:
+            raise NotImplementedError("remap: the quantiser's index remapping (quantize.py:229-241) is not built; no shipped config sets it")
+        if fusion != "concat":
+            raise NotImplementedError(f"fusion={fusion!r}: only the 'concat' fusion of the scales is built (msvqgan.py:59-66; every shipped config)")
+        if edconfig.get("double_z") or ddconfig.get("double_z"):
+            raise NotImplementedError("double_z=True: a quantised model has no use for the doubled moments (every shipped config sets double_z: False)")
+        if colorize_nlabels is not None:
+            raise NotImplementedError("colorize_nlabels: the random `colorize` projection of segmentation inputs (to_rgb, msvqgan.py:311-317) is not built")
+        assert len(n_embed) == edconfig["multiscale"], "multiscale mode. dim of n_embed is incorrect."
+        assert len(n_embed) == len(embed_dim), "multiscale mode. dim of n_embed is incorrect."
+        self.image_key, self.fusion = image_key, fusion
+        self.embed_dim, self.n_embed = embed_dim, n_embed
+        self.use_aux_loss, self.unsample_type = use_aux_loss, unsample_type
+        self.sane_index_shape, self.quant_beta, self.legacy = sane_index_shape, quant_beta, legacy
+        self.edconfig, self.ddconfig = edconfig, ddconfig
+        self.vq_cfg = dict(embed_dim=embed_dim, n_embed=n_embed, edconfig=edconfig, ddconfig=ddconfig, quant_beta=float(quant_beta),
+                           legacy=bool(legacy))
+        self.precision = precision
+        holders.build_msvqgan_params(self, edconfig, ddconfig, n_embed, embed_dim)
+        for i, q in enumerate(self.ms_quantize):
+            q.n_e, q.e_dim, q.beta, q.legacy, q.sane_index_shape = n_embed[i], embed_dim[i], quant_beta, legacy, sane_index_shape
+        self.encoder.num_resolutions = len(edconfig["ch_mult"])
+        self.encoder.multiscale = edconfig["multiscale"]
+        self.encoder.resolution = edconfig["resolution"]
+        # lossconfig: VQLPIPSWithDiscriminator is LPIPS (VGG weights: a download) + a PatchGAN trained by the backward pass -- whatever
+        # the target, the module holds the no-op loss (like VQModelInterface)
+        self.loss = DummyLoss()
+        nres = len(edconfig["ch_mult"])
+        self.res_list = [edconfig["resolution"] / 2 ** (nres - i - 1) for i in range(edconfig["multiscale"])]
+        if monitor is not None:
+            self.monitor = monitor
+        self._init_versioning()
+        if ckpt_path is not None:
+            self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
+
+    init_from_ckpt = VQModelInterface.init_from_ckpt
+
+    def runtime(self):
+        from .runtime import DecoderRuntime
+        dev = next(self.parameters()).device
+        key = (str(dev), self.precision or config.PRECISION)
+        if self._rt is None or self._rt_key != key:
+            if dev.type != "cuda":
+                _no_cpu("MSFPNVQModel", dev)
+            self._rt = DecoderRuntime(self, self.vq_cfg, dev, key[1])
+            self._rt_key = key
+        return self._rt
+
+    def _check_image(self, x, what):
+        if x.shape[1] > 3:
+            raise NotImplementedError(f"{what}: inputs with more than 3 channels (segmentation maps through to_rgb's random `colorize` "
+                                      "projection, msvqgan.py:283-287,311-317) are not built")
+        if not x.is_cuda:
+            _no_cpu(what, x.device)
+
+    def _info(self, idx, B, h, w):
+        """msvqgan.py:121,142-143 with VectorQuantizer2's (perplexity, min_encodings, min_encoding_indices) = (None, None, idx)."""
+        n = len(idx)
+        if self.sane_index_shape:       # quantize.py:304-306
+            idx = [i.view(B, h >> (n - 1 - s), w >> (n - 1 - s)) for s, i in enumerate(idx)]
+        return [[None] * n, [None] * n, list(idx)]
+
+    @torch.no_grad()
+    def encode(self, x):
+        """msvqgan.py:116-154: image (B, 3, H, W) -> (quant, emb_loss, info_ms).  quant: channels [fine .. coarse], each scale the
+        reference's z + (z_q - z) in fp32; emb_loss: 0-d f32, the scales' losses added coarse to fine; info_ms[2]: int64 codes per scale,
+        coarse first."""
+        self._check_image(x, "MSFPNVQModel.encode")
+        from . import autoplanes
+        quant, loss, idx = autoplanes.run(self, lambda _n: self.runtime().encode_quant(x), "MSFPNVQModel.encode")
+        return quant, loss, self._info(idx, quant.shape[0], quant.shape[2], quant.shape[3])
+
+    @torch.no_grad()
+    def decode(self, quant, to_uint8=False):
+        """msvqgan.py:156-159: post_quant_conv + decoder on an already quantised [fine .. coarse] latent -- NO VQ lookup (that is
+        VQModelInterface.decode).  to_uint8 as on VQModelInterface.decode."""
+        if not quant.is_cuda:
+            _no_cpu("MSFPNVQModel.decode", quant.device)
+        from . import autoplanes
+        return autoplanes.run(self, lambda _n: self.runtime().decode_quant(quant.contiguous().float(), to_uint8=to_uint8), "MSFPNVQModel.decode")
+
+    def decode_code(self, code_b):
+        raise NotImplementedError("decode_code: the reference's own reads `self.quantize`, which the multi-scale model does not have (it raises "
+                                  "AttributeError, msvqgan.py:161-164); decode given codes with VQModelInterface.decode(force_codes=...)")
+
+    @torch.no_grad()
+    def forward(self, input, return_info=False):
+        """msvqgan.py:166-186: (dec, diff, info), or (dec, [dec_aux, dec_aux2], diff, info) under use_aux_loss.  Encoder, loss and decoder
+        replay as one captured graph per input shape; the two aux decodes (quant with all but its last / its first embed_dim[-1] channels
+        zeroed) run only under use_aux_loss, batched with the main decode."""
+        return self._reconstruct(input)[0]
+
+    def _reconstruct(self, x):
+        """(what forward returns, quant)."""
+        self._check_image(x, "MSFPNVQModel.forward")
+        aux = bool(self.use_aux_loss)
+        from . import autoplanes
+        dec, quant, diff, idx = autoplanes.run(self, lambda _n: self.runtime().reconstruct(x, aux=aux), "MSFPNVQModel.forward")
+        info = self._info(idx, quant.shape[0], quant.shape[2], quant.shape[3])
+        if aux:
+            B = x.shape[0]
+            return (dec[:B], [dec[B:2 * B], dec[2 * B:]], diff, info), quant
+        return (dec, diff, info), quant
+
+    def get_input(self, batch, k):
+        """msvqgan.py:188-193."""
+        x = batch[k]
+        if len(x.shape) == 3:
+            x = x[..., None]
+        x = x.permute(0, 3, 1, 2).to(memory_format=torch.contiguous_format)
+        return x.float()
+
+    def get_img_ids(self, batch):
+        """msvqgan.py:195-197."""
+        return batch["file_name"]
+
+    def get_last_layer(self):
+        return self.decoder.conv_out.weight
+
+    def training_step(self, batch, batch_idx, optimizer_idx=0):
+        raise FridoHipError("training_step: no backward pass exists on the HIP path (encode / decode / forward / log_images evaluate the "
+                            "tokenizer without gradients)")
+
+    def configure_optimizers(self):
+        raise FridoHipError("configure_optimizers: no backward pass exists on the HIP path, so there is nothing to optimise")
+
+    def validation_step(self, batch, batch_idx):
+        raise NotImplementedError("validation_step: its loss module is LPIPS + a PatchGAN discriminator (VQLPIPSWithDiscriminator), whose weights "
+                                  "are a download / come from training; the part of the objective that exists here is the codebook loss, encode()[1]")
+
+    def test_step(self, batch, batch_idx):
+        """msvqgan.py:244-245."""
+        return None
+
+    @torch.no_grad()
+    def log_images(self, batch, **kwargs):
+        """msvqgan.py:266-309: inputs, reconstructions, codebook_info, file_name when the batch has it, reconstructions_aux under
+        use_aux_loss, and per scale the decode of quant with every other scale's channels zeroed -- all scales as one decoder batch."""
+        log = dict()
+        x = self.get_input(batch, self.image_key)
+        try:
+            log["file_name"] = self.get_img_ids(batch)
+        except Exception:
+            pass
+        x = x.to(self.device)
+        out, quant = self._reconstruct(x)
+        if self.use_aux_loss:
+            xrec, xrec_aux, _, info = out
+            log["reconstructions_aux"] = xrec_aux
+        else:
+            xrec, _, info = out
+        log["codebook_info"] = [info[2]]
+        log["inputs"] = x
+        log["reconstructions"] = xrec
+        if len(self.embed_dim) >= 2:
+            # (the reference encodes x a second time here, msvqgan.py:294: the same quant)
+            groups = [(sum(self.embed_dim[:i]), sum(self.embed_dim[:i + 1])) for i in range(len(self.embed_dim))]
+            from . import autoplanes
+            recs = autoplanes.run(self, lambda _n: self.runtime().decode_quant(quant, groups=groups), "MSFPNVQModel.log_images")
+            B = x.shape[0]
+            for i, (c0, c1) in enumerate(groups):
+                log[f"reconstructions_{c0}_{c1}"] = recs[i * B:(i + 1) * B]
+        return log
 
 
 PLAN_CACHE_SIZE = 4      # compiled cond-stage plans kept per (batch, tokens) shape (like samplers.ENGINE_CACHE_SIZE)

@@ -6,7 +6,8 @@
                      (reference: frido/models/diffusion/ddim.py:116-273, plms.py:116-303); kind="ddpm": the
                      ancestral loop of frido/models/diffusion/frido.py:1308-1418 on the same machinery;
   ancestral_step   — one ancestral update outside a loop (FridoDiffusion.p_mean_variance / p_sample);
-  DecoderRuntime   — VQModelInterface.decode / decode_first_stage on the HIP engine.
+  DecoderRuntime   — VQModelInterface.decode / decode_first_stage on the HIP engine; MSFPNVQModel's encode_quant / decode_quant /
+                     reconstruct (encode program, codebook loss and decode program as one captured graph).
 """
 import os
 
@@ -18,7 +19,7 @@ from .builder import Builder
 from .engine import current_stream_ptr, require_gpu
 from .schedules import ancestral_table, sampler_coef_table
 from .unet_plan import UNetStagePlan
-from .vqgan_plan import VQDecodePlan, VQEncodePlan
+from .vqgan_plan import VQDecodePlan, VQDecodeQuantPlan, VQEncodePlan
 
 # step bodies per captured DDIM graph (1 = one graph launch per step, the r01-r05 form; r06 default 20: 10 measured +0.17 %, 40 +0.28 % end to end, interleaved,
 # profiles/r06_graph_steps_ab.txt); see SamplerEngine._ddim_stage
@@ -818,6 +819,8 @@ class DecoderRuntime:
         self.nsplit = config.nsplit(precision)
         self.b = Builder(self.device, self.nsplit, _weights_of(module, self.device), planes=self.planes)
         self.plans = {}
+        self.graphs = {}         # reconstruct(): (B, H, W, aux) -> the captured encode + loss + decode graph
+        self.graph_captures = 0
 
     U8_MODES = {False: 0, None: 0, True: 1, "np": 1, "pil": 2}
 
@@ -871,6 +874,98 @@ class DecoderRuntime:
         x_in.copy_(x)            # plumbing: D2D copy into the plan's fixed input buffer
         plan.prog.run(st)
         return plan.out.clone()
+
+    # ---- the MS-VQGAN as a model of its own (MSFPNVQModel: taming/models/msvqgan.py:116-186, 266-309) ----
+    def _encq(self, B, Cin, H, W):
+        """(input buffer, quantised encode plan, its loss state) of one image shape."""
+        key = ("encq", B, H, W)
+        if key not in self.plans:
+            from .vqloss import CommitLoss
+            embed = self.cfg["embed_dim"]
+            x_in = torch.zeros(B, Cin, H, W, dtype=torch.float32, device=self.device)
+            plan = VQEncodePlan(self.b, self.cfg, B=B, H=H, W=W, x_in=x_in, scale=[1.0] * len(embed), quantized=True)
+            loss = CommitLoss(plan, embed, self.cfg.get("quant_beta", 0.25), self.cfg.get("legacy", True), self.device)
+            self.plans[key] = (x_in, plan, loss)
+        return self.plans[key]
+
+    def _decq(self, Bs, h, w, groups, u8, src=None):
+        """(input buffer, decode-from-quant plan); src: another plan's quant tensor to read instead of an input buffer of its own."""
+        key = ("decq", Bs, h, w, groups, u8, None if src is None else src.data_ptr())
+        if key not in self.plans:
+            embed = self.cfg["embed_dim"]
+            q_in = src if src is not None else torch.zeros(Bs, sum(embed), h, w, dtype=torch.float32, device=self.device)
+            self.plans[key] = (q_in, VQDecodeQuantPlan(self.b, self.cfg["ddconfig"], embed, Bs=Bs, h=h, w=w, quant_src=q_in,
+                                                       groups=groups, u8_mode=u8))
+        return self.plans[key]
+
+    def _stream_obj(self):
+        if getattr(self, "_stream", None) is None:
+            self._stream = torch.cuda.Stream(device=self.device)
+        return self._stream
+
+    @_lib.with_planes
+    def encode_quant(self, x):
+        """x (B, 3, H, W) NCHW image -> (quant (B, sum(embed), H/f, W/f): the quantised multi-scale latent, channels [fine .. coarse],
+        emb_loss: 0-d f32, [idx_s]: int64 [B * h_s * w_s] per scale, coarse first) -- device tensors; the encode program and the loss
+        launcher go out on the current stream and nothing waits for them."""
+        from .vqloss import launch_vq_commit_loss
+        B, Cin, H, W = x.shape
+        x_in, plan, loss = self._encq(B, Cin, H, W)
+        st = current_stream_ptr(self.device)
+        x_in.copy_(x)            # plumbing: D2D copy into the plan's fixed input buffer
+        plan.prog.run(st)
+        launch_vq_commit_loss(loss.desc, st)
+        return plan.quant.clone(), loss.total.clone(), [i.clone() for i in plan.idx]
+
+    @_lib.with_planes
+    def decode_quant(self, quant, to_uint8=False, groups=None):
+        """quant (B, sum(embed), h, w) NCHW, already quantised, channels [fine .. coarse] -> image (B, 3, H, W): post_quant_conv + decoder,
+        no VQ lookup.  groups: channel ranges (c0, c1) -- the result is (len(groups) * B, 3, H, W), entries g * B ... decoded from quant with
+        everything outside group g's range zeroed, all as one batch.  to_uint8 as in decode()."""
+        B, Ct, h, w = quant.shape
+        assert Ct == sum(self.cfg["embed_dim"]), f"the quantised latent has {sum(self.cfg['embed_dim'])} channels, got {Ct}"
+        u8 = self.U8_MODES[to_uint8]
+        groups = None if groups is None else tuple(tuple(int(v) for v in g) for g in groups)
+        q_in, plan = self._decq(B, h, w, groups, u8)
+        q_in.copy_(quant)
+        plan.prog.run(current_stream_ptr(self.device))
+        return (plan.out_u8 if u8 else plan.out).clone()
+
+    def aux_groups(self):
+        """Channel ranges of MSFPNVQModel.forward's three decodes (msvqgan.py:168-177): everything, the last embed_dim[-1] channels, the
+        first embed_dim[-1] channels."""
+        embed = self.cfg["embed_dim"]
+        Ct = sum(embed)
+        return ((0, Ct), (Ct - embed[-1], Ct), (0, embed[-1]))
+
+    @_lib.with_planes
+    def reconstruct(self, x, aux=False, use_graph=True):
+        """MSFPNVQModel.forward (msvqgan.py:166-186): encode program -> loss launcher -> decode program as ONE captured graph per
+        (B, H, W, aux), replayed on later batches; quant stays on the device between the halves.  aux: the three decodes of :168-177 as one
+        decoder program at batch 3B.  Returns (dec (B or 3B, 3, H, W), quant, emb_loss, [idx_s])."""
+        from .patching import PatchProg
+        from .vqloss import VQLOSS
+        B, Cin, H, W = x.shape
+        x_in, enc, loss = self._encq(B, Cin, H, W)
+        h, w = enc.quant.shape[2:]
+        _, dec = self._decq(B, h, w, self.aux_groups() if aux else None, 0, src=enc.quant)
+        stream = self._stream_obj()
+        stream.wait_stream(torch.cuda.current_stream(self.device))
+        sp = stream.cuda_stream
+        with torch.cuda.stream(stream):
+            x_in.copy_(x)
+            key = ("rec", B, H, W, bool(aux), bool(use_graph))
+            if key not in self.graphs:
+                prog = PatchProg(self.device, self.nsplit)
+                prog.ops = list(enc.prog.ops) + [(VQLOSS, loss.desc)] + list(dec.prog.ops)
+                prog.keep = [enc, loss, dec]
+                self.graphs[key] = prog.capture(sp) if use_graph else prog
+                self.graph_captures += 1
+            g = self.graphs[key]
+            g.launch(sp) if use_graph else g.run(sp)
+            out = dec.out.clone(), enc.quant.clone(), loss.total.clone(), [i.clone() for i in enc.idx]
+        torch.cuda.current_stream(self.device).wait_stream(stream)
+        return out
 
     # ---- patch-wise mode (FridoDiffusion.split_input_params with patch_distributed_vq, frido.py:840-877, 963-993) ----
     @_lib.with_planes

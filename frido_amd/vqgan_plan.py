@@ -145,12 +145,51 @@ class VQDecodePlan:
         z_op.free()
 
 
+class VQDecodeQuantPlan:
+    """MSFPNVQModel.decode (msvqgan.py:156-159): post_quant_conv + Decoder on an ALREADY quantised latent -- the decode plan entered after
+    its VQ stage.  `quant_src`: device f32 NCHW [Bs][Ct][h][w], channels [fine .. coarse].  `groups`: channel ranges (c0, c1); the plan
+    decodes len(groups) * Bs latents as ONE batch, group g (entries g * Bs ...) being quant_src with everything outside [c0, c1) zero --
+    the masked copies of MSFPNVQModel.forward's aux decodes (msvqgan.py:168-177) and of log_images' per-scale reconstructions (:296-307)
+    are written straight into the program's input; the channels a group leaves out stay at the zero they were allocated with.
+    The image comes out NCHW in `out` (or, u8_mode, as the uint8 HWC image `out_u8` of the last conv's epilogue)."""
+
+    def __init__(self, b: Builder, ddconfig, embed_dim, *, Bs, h, w, quant_src, groups=None, u8_mode=0):
+        self.b = b
+        a = self.a = decoder_arch(ddconfig, "decoder")
+        Ct, hw, dev = sum(embed_dim), h * w, b.device
+        groups = [(0, Ct)] if groups is None else [tuple(g) for g in groups]
+        assert all(0 <= c0 < c1 <= Ct for c0, c1 in groups), groups
+        B = self.B = len(groups) * Bs
+        up_levels = sum(1 for blk in a.body if blk.kind == "up")
+        self.H, self.W = h << up_levels, w << up_levels
+        self.z_state = torch.zeros(B * hw, Ct, dtype=torch.float32, device=dev)
+        self.out_u8 = torch.zeros(B, self.H, self.W, a.out_ch, dtype=torch.uint8, device=dev) if u8_mode else None
+        self.out_nhwc = None if u8_mode else torch.zeros(B * self.H * self.W, a.out_ch, dtype=torch.float32, device=dev)
+        self.out = None if u8_mode else torch.zeros(B, a.out_ch, self.H, self.W, dtype=torch.float32, device=dev)
+        prog = self.prog = b.new_prog()
+        for g, (c0, c1) in enumerate(groups):
+            b.relayout(quant_src.data_ptr(), self.z_state.data_ptr() + 4 * g * Bs * hw * Ct, Bs, hw, Ct, c0, c1 - c0, Ct, c0, 0)
+        q_op = b.pack(self.z_state.data_ptr(), 1, B * hw, Ct, 0, Ct)
+        pq = b.linear(q_op, "post_quant_conv", out="f32_strict")
+        q_op.free()
+        z_op = b.pack(pq.ptr, 1, B * hw, pq.C, 0, pq.C)
+        pq.free()
+        decoder_body(b, B, ddconfig, "decoder", z_op, h, w, ("u8", self.out_u8, u8_mode) if u8_mode else ("f32", _T(self.out_nhwc)))
+        z_op.free()
+        if not u8_mode:
+            b.relayout(self.out_nhwc.data_ptr(), self.out.data_ptr(), B, self.H * self.W, a.out_ch, 0, a.out_ch, a.out_ch, 0, 1)
+        prog.keep.append(quant_src)
+
+
 class VQEncodePlan:
     """VQModelInterface.encode (msvqgan.py:326-374): MSEncoder (model.py:512-546) -> coarse-to-fine pre-quant features
     (quant_conv, VQ, ConvTranspose upsample, shared decoder) -> nearest-upsampled channel concat [coarse .. fine],
     optionally scaled per scale like get_first_stage_encoding (frido.py:654-662)."""
 
-    def __init__(self, b: Builder, vq_cfg, *, B, H, W, x_in, scale):
+    def __init__(self, b: Builder, vq_cfg, *, B, H, W, x_in, scale, quantized=False):
+        """quantized: the MSFPNVQModel.encode form (msvqgan.py:116-154) -- the finest scale is quantised too, every scale keeps its codes
+        (`idx`) and its quantised map (`zq`, next to the pre-quant `h_out`), and the output is `quant`: the quantised maps, nearest-upsampled,
+        channels [fine .. coarse] (the reference reverses before its concat); the pre-quant concat `out` is not assembled."""
         from .arch import encoder_arch
         from .holders import shared_decoder_cfg
         self.b = b
@@ -183,7 +222,7 @@ class VQEncodePlan:
             hcur.free()
             heads.append((ao, fh, fw, a.z_channels[i]))
         heads = heads[::-1]          # coarse first
-        self.h_out = []
+        self.h_out, self.zq, self.idx = [], [], []
         prev = []                    # quantised maps of coarser scales: (f32 tensor [B*hw][e], h, w)
         for ii in range(n):
             ao, fh, fw, zc = heads[ii]
@@ -231,15 +270,30 @@ class VQEncodePlan:
             b.linear(q_op, f"ms_quant_conv.{ii}", out=("f32", _T(hq)))
             q_op.free()
             self.h_out.append((hq, fh, fw))
-            if ii < n - 1:
+            if ii < n - 1 or quantized:
                 zq = torch.zeros(B * hw, embed[ii], dtype=torch.float32, device=dev)
                 b._persist.append(zq)
+                idx = None
+                if quantized:
+                    idx = torch.zeros(B * hw, dtype=torch.int64, device=dev)
+                    b._persist.append(idx)
+                    self.idx.append(idx)
+                    self.zq.append((zq, fh, fw))
                 cb = b.dev_f32(f"ms_quantize.{ii}.embedding.weight")
                 prog.emit("FRIDO_OP_VQ", x=hq.data_ptr(), npix=B * hw, Cx=embed[ii], c0=0, e=embed[ii], inv_scale=1.0,
-                          codebook=cb.data_ptr(), n_codes=n_embed[ii], zq=zq.data_ptr(), Cq=embed[ii], q0=0, idx=None)
+                          codebook=cb.data_ptr(), n_codes=n_embed[ii], zq=zq.data_ptr(), Cq=embed[ii], q0=0,
+                          idx=idx.data_ptr() if quantized else None)
                 prev.append((zq, fh, fw))
         for t, _, _ in level_out:
             t.free()
+        if quantized:
+            # channel concat [fine, ..., coarse] of the quantised maps, every scale nearest-upsampled to the finest grid (msvqgan.py:146-152)
+            fh, fw = self.zq[-1][1], self.zq[-1][2]
+            self.quant = torch.zeros(B, sum(embed), fh, fw, dtype=torch.float32, device=dev)
+            for i, (zq, hh, ww) in enumerate(self.zq):
+                prog.emit("FRIDO_OP_PLACE", src=zq.data_ptr(), dst=self.quant.data_ptr(), B=B, h=hh, w=ww, Csrc=embed[i], c0=0,
+                          Cuse=embed[i], Cdst=sum(embed), d0=sum(embed[i + 1:]), up_shift=(fh // hh).bit_length() - 1, scale=1.0)
+            return
         # channel concat [coarse, ..., fine], every scale nearest-upsampled to the finest grid
         fh, fw = self.h_out[-1][1], self.h_out[-1][2]
         self.out = torch.zeros(B, sum(embed), fh, fw, dtype=torch.float32, device=dev)

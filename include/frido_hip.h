@@ -481,6 +481,25 @@ typedef struct FridoDiffusionLoss { const float* pred; const int64_t* t; const f
                                     int32_t B, HW, Cx, ch_start, nch, T, rng_stream, loss_type;
                                     float l_simple_weight, original_elbo_weight; } FridoDiffusionLoss;
 
+/* ---- the MS-VQGAN's codebook loss: MSFPNVQModel.encode (taming/models/msvqgan.py:116-154), VectorQuantizer2.forward
+ * (taming/modules/vqvae/quantize.py:286-291) ----
+ * Not an op kind: an exported launcher with a descriptor of its own (frido_vq_commit_loss below), run eagerly or between
+ * frido_capture_begin and frido_capture_end.  Up to FRIDO_VQLOSS_MAX_SCALES scales, coarse first; scale k compares the channel slice
+ * [c0, c0 + e) of two NHWC f32 maps z[k], zq[k] of npix[k] rows C[k] wide (z: the quantiser's input, zq: its output):
+ *   m_k = mean over npix * e elements of (zq - z)^2 -- difference and square in fp32, each rounded on its own, the sum in f64 in a fixed
+ *         order (no atomics: the same bits on every launch; the order depends on the scale's own size only, so m_k does not depend on
+ *         which other scales share the call), the mean rounded to fp32;
+ *   out[k] = m_k;   *emb_loss = 0 + l_0 + l_1 + ... in fp32, l_k = m_k + beta * m_k (legacy != 0) or beta * m_k + m_k (legacy == 0).
+ * A first launch writes per-workgroup f64 partials (at most FRIDO_VQLOSS_MAX_WG per scale) into `partials`, a caller-owned buffer of
+ * FRIDO_VQLOSS_WS_BYTES bytes (16-byte aligned; it needs no initialisation); a second one-workgroup launch on the same stream adds them
+ * in index order.  C, c0 and e multiples of 4: 16-byte accesses (z and zq 16-byte aligned); anything else, the shipped e = 3 included,
+ * reads scalars. */
+#define FRIDO_VQLOSS_MAX_SCALES 4
+#define FRIDO_VQLOSS_MAX_WG 256
+#define FRIDO_VQLOSS_WS_BYTES 8192      /* MAX_SCALES * MAX_WG doubles */
+typedef struct FridoVqCommitLoss { const float* z[4]; const float* zq[4]; int64_t npix[4]; int32_t C[4], c0[4], e[4];
+                                   double* partials; float* out; float* emb_loss; float beta; int32_t n_scales, legacy; } FridoVqCommitLoss;
+
 enum FridoOpKind {
     FRIDO_OP_GEMM = 1, FRIDO_OP_GN_STATS, FRIDO_OP_GN_APPLY, FRIDO_OP_LAYERNORM, FRIDO_OP_SOFTMAX,
     FRIDO_OP_GEGLU, FRIDO_OP_PACK, FRIDO_OP_RELAYOUT, FRIDO_OP_VQ, FRIDO_OP_SAMPLER_STEP,
@@ -570,6 +589,9 @@ int frido_fold(const FridoFold* d, frido_stream_t s);
 /* ---- the diffusion objective (descriptors above); bad arguments return FRIDO_EINVAL before any device is touched ---- */
 int frido_qsample(const FridoQSample* d, frido_stream_t s);
 int frido_diffusion_loss(const FridoDiffusionLoss* d, frido_stream_t s);
+
+/* ---- the MS-VQGAN's codebook loss (descriptor above); bad arguments return FRIDO_EINVAL before any device is touched ---- */
+int frido_vq_commit_loss(const FridoVqCommitLoss* d, frido_stream_t s);
 
 /* ---- timing on the launch stream (HIP events) ---- */
 int frido_event_create(void** ev);
