@@ -69,6 +69,15 @@ def sample_images(model, cond, *, S, eta=1.0, sampler="ddim", scale=1.0, uncond=
             raise ValueError(f"sampler='ddpm': the ancestral loop runs all {model.num_resulotion} stages of the model (got num_stage={num_stage})")
         z = model.p_sample_loop(cond, (b,) + shape, timesteps=S, verbose=False, log_every_t=log_every_t, noise=noise, seed=seed,
                                 sample0=sample0)
+    elif sampler == "dpm":
+        # DPM-Solver++(2M), 2nd order on the logSNR grid (DPMSolverSampler's defaults): deterministic, so eta -- this function's default is
+        # DDIM's 1.0 -- has nothing to set; any other value is refused
+        if eta not in (0.0, 1.0):
+            raise ValueError(f"sampler='dpm': the solver is deterministic and has no eta (got {eta}; leave it at its default)")
+        from .samplers import DPMSolverSampler
+        z, _ = DPMSolverSampler(model).sample(S=S, batch_size=b, shape=shape, conditioning=cond, num_stage=num_stage or unet.num_stage,
+                                              verbose=False, unconditional_guidance_scale=scale, unconditional_conditioning=uncond,
+                                              noise=noise, seed=seed, sample0=sample0, log_every_t=log_every_t)
     else:
         cls = PLMSSampler if sampler == "plms" else DDIMSampler
         z, _ = cls(model).sample(S=S, batch_size=b, shape=shape, conditioning=cond, num_stage=num_stage or unet.num_stage,

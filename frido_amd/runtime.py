@@ -4,7 +4,8 @@
   SamplerEngine    — the multi-stage DDIM / PLMS loop with per-sample invariants hoisted, the per-step
                      body captured in a hipGraph, a device step counter and coefficient tables
                      (reference: frido/models/diffusion/ddim.py:116-273, plms.py:116-303); kind="ddpm": the
-                     ancestral loop of frido/models/diffusion/frido.py:1308-1418 on the same machinery;
+                     ancestral loop of frido/models/diffusion/frido.py:1308-1418 on the same machinery; kind="dpm":
+                     DPM-Solver++(2M), which the reference does not have, in DDIM's loop (frido_dpm_step as the update);
   ancestral_step   — one ancestral update outside a loop (FridoDiffusion.p_mean_variance / p_sample);
   DecoderRuntime   — VQModelInterface.decode / decode_first_stage on the HIP engine; MSFPNVQModel's encode_quant / decode_quant /
                      reconstruct (encode program, codebook loss and decode program as one captured graph).
@@ -17,13 +18,16 @@ import torch
 from . import _lib, config
 from .builder import Builder
 from .engine import current_stream_ptr, require_gpu
-from .schedules import ancestral_table, sampler_coef_table
+from .patching import FOREIGN
+from .schedules import ancestral_table, dpm_solver_table, sampler_coef_table
 from .unet_plan import UNetStagePlan
 from .vqgan_plan import VQDecodePlan, VQDecodeQuantPlan, VQEncodePlan
 
 # step bodies per captured DDIM graph (1 = one graph launch per step, the r01-r05 form; r06 default 20: 10 measured +0.17 %, 40 +0.28 % end to end, interleaved,
 # profiles/r06_graph_steps_ab.txt); see SamplerEngine._ddim_stage
 GRAPH_STEPS = max(1, int(os.environ.get("FRIDO_GRAPH_STEPS", "20")))
+DPM_STEP = "dpm_step"
+FOREIGN[DPM_STEP] = "frido_dpm_step"      # op tag of the DPM-Solver++ update inside a step body (patching.PatchProg)
 
 
 def _weights_of(module, device):
@@ -192,7 +196,8 @@ class SamplerEngine:
             self._init(builder, cfg, **kw)
 
     def _init(self, builder: Builder, cfg, *, B, C, H, W, nctx, S, eta, kind, alphas_cumprod, embed_dim, cfg_scale=1.0,
-              use_graph=True, num_stage=None, temperature=1.0, posterior=None, clip=False, patch=None):
+              use_graph=True, num_stage=None, temperature=1.0, posterior=None, clip=False, patch=None, order=2, skip_type="logSNR",
+              lower_order_final=True):
         self.b, self.cfg = builder, cfg
         self.dev = builder.device
         self.B, self.C, self.H, self.W, self.nctx = B, C, H, W, nctx
@@ -210,6 +215,10 @@ class SamplerEngine:
             tab, self.t_loop = ancestral_table(posterior, None, clip_denoised=clip), np.arange(S - 1, -1, -1)
             assert 0 < S <= tab.shape[0], f"ancestral chain of {S} steps on a schedule of {tab.shape[0]}"
             self.row0 = tab.shape[0] - S
+        elif kind == "dpm":
+            # DPM-Solver++(2M): the grid (skip_type) is part of the solver; every stage walks the table from row 0, a first-order row
+            assert patch is None, "the DPM-Solver loop has no patch-wise mode"
+            self.t_loop, tab = dpm_solver_table(np.asarray(alphas_cumprod, dtype=np.float64), S, skip_type, order, lower_order_final)
         else:
             tab, self.t_loop = sampler_coef_table(np.asarray(alphas_cumprod, dtype=np.float32), S, eta, plms=(kind == "plms"))
         self.n_steps = S if kind == "ddpm" else tab.shape[0]
@@ -254,6 +263,9 @@ class SamplerEngine:
             self.hist_stride = B * H * W * nmax
             self.hist = torch.zeros(4, self.hist_stride, dtype=torch.float32, device=self.dev)    # eps ring, slot = step & 3
             self.x_save = torch.zeros_like(self.x)
+        if kind == "dpm":
+            # the previous step's x0 prediction, one buffer per stage [B * HW][nch]; zero until the stage's first step has run
+            self.x0_hist = [torch.zeros(B * H * W, self.embed[s], dtype=torch.float32, device=self.dev) for s in range(self.num_stage)]
         if kind == "ddpm":
             # host-noise form: the tape and the coefficient rows of ONE replay unit (up to GRAPH_STEPS steps), read through a counter of
             # their own that restarts with every unit -- a T = 1000 tape of a whole stage would be gigabytes at B = 16
@@ -275,8 +287,9 @@ class SamplerEngine:
             prog.emit("FRIDO_OP_STEP_ADD", step=self.step_bx.data_ptr(), delta=delta * self.Bm * self.xrep)
 
     def _prog(self):
-        """An empty program for a step body: in patch mode one whose op list may hold the unfold / fold launches."""
-        if self.geo is not None:
+        """An empty program for a step body: in patch mode one whose op list may hold the unfold / fold launches, for the DPM solver
+        one that may hold its update (an exported launcher too, not an op kind)."""
+        if self.geo is not None or self.kind == "dpm":
             from .patching import PatchProg
             return PatchProg(self.dev, self.b.nsplit)
         from .engine import Prog
@@ -328,6 +341,16 @@ class SamplerEngine:
             kw[f"hist{i + 1}"] = h
         return kw
 
+    def _dpm_desc(self, s):
+        """FridoDpmStep of stage s on the engine's state: what _sampler_op gives the DDIM update, and the stage's x0 history."""
+        start, nch = sum(self.embed[:s]), self.embed[s]
+        BHW = self.B * self.H * self.W
+        return _lib.STRUCTS["FridoDpmStep"](
+            x=self.x.data_ptr(), B=self.B, HW=self.H * self.W, Cx=self.C, start=start, nch=nch, eps_cond=self._eps_ptr(s),
+            eps_uncond=self._eps_ptr(s) + 4 * BHW * nch if self.xrep == 2 else None, cfg_scale=self.cfg_scale, cfg_dev=self.cfg_dev.data_ptr(),
+            coef=self.coef.data_ptr(), step=self.step.data_ptr(), coef_row_offset=0, x_out=self.x.data_ptr(), pred_x0=self.pred_x0.data_ptr(),
+            x0_hist=self.x0_hist[s].data_ptr())
+
     def _upload_noise(self, s, tape):
         """tape: list of per-step NCHW tensors (B, 3(s+1), H, W) in draw order -> the stage's persistent NHWC device buffer
         (fixed address: the captured step body of the tape mode reads it by step index)."""
@@ -357,6 +380,9 @@ class SamplerEngine:
         Returns (samples NCHW, intermediates dict)."""
         B, C, H, W = self.B, self.C, self.H, self.W
         assert self.kind != "ddpm", "an ancestral engine runs through run_ancestral()"
+        if self.kind == "dpm" and (noise_dropout > 0. or score_corrector is not None):
+            raise NotImplementedError("the DPM-Solver loop is deterministic and has no hook between the denoiser and the update: "
+                                      "noise_dropout / score_corrector are not built for it")
         self._opts = dict(noise_dropout=float(noise_dropout), score_corrector=score_corrector, corrector_kwargs=dict(corrector_kwargs or {}),
                           model=model, cond=cond, uncond=uncond)
         if noise_dropout > 0. and noise == "philox":
@@ -411,7 +437,7 @@ class SamplerEngine:
                 if self.labels:
                     self.step_bx.zero_()
                 self._run_pre(plan, sp)
-                if self.kind == "ddim":
+                if self.kind in ("ddim", "dpm"):
                     self._ddim_stage(s, sp, draw, seed, sample0, inter, log_every_t, callback, img_callback, Cs)
                 else:
                     self._plms_stage(s, sp, draw, seed, sample0, inter, log_every_t, callback, img_callback, Cs)
@@ -464,7 +490,18 @@ class SamplerEngine:
             draw = lambda shape: torch.nn.functional.dropout(base(shape), p=p_drop)
         if opts.get("score_corrector") is not None:
             return self._ddim_stage_with_corrector(s, sp, draw, seed, sample0, inter, log_every_t, callback, img_callback, Cs, opts)
-        if draw is not None:
+        if self.kind == "dpm":
+            # DPM-Solver++(2M): no noise after x_T (the host generator is left alone); the body is model evaluation, frido_dpm_step, counter add
+            key = ("dpm", s)
+            if key not in self.graphs:
+                body = self._prog()
+                body.ops = self._eval_ops(s) + [(DPM_STEP, self._dpm_desc(s))]
+                self._step_add(body, 1)
+                body.keep = [plan]
+                self.graphs[key] = body.capture(sp) if self.use_graph else body
+            g = self.graphs[key]
+            launch = (lambda: g.launch(sp)) if self.use_graph else (lambda: g.run(sp))
+        elif draw is not None:
             noise_ptr, noise_C = self._upload_noise(s, [draw((self.B, Cs, self.H, self.W)) for _ in range(n)])
             key = ("ddim_tape", s)
             if key not in self.graphs:

@@ -1,5 +1,6 @@
 """DDIMSampler / PLMSSampler with the reference's constructor and `.sample(...)` signature
-(frido/models/diffusion/ddim.py:11-114, plms.py:11-114), driving the HIP SamplerEngine.
+(frido/models/diffusion/ddim.py:11-114, plms.py:11-114), driving the HIP SamplerEngine; DPMSolverSampler, which the reference does not
+have (upstream latent-diffusion ships one with this signature): DPM-Solver++(2M) on the same engine.
 
 Noise: the reference draws x_T and one torch.randn per update from torch's global generator of the device it runs on.
 With noise="torch" (default) the same draws are made from the HOST generator in the same order and uploaded, so a run after
@@ -155,3 +156,81 @@ class DDIMSampler(_SamplerBase):
 
 class PLMSSampler(_SamplerBase):
     KIND = "plms"
+
+
+class DPMSolverSampler(_SamplerBase):
+    """DPM-Solver++(2M) (Lu et al. 2022: data prediction, multistep): DDIM's `.sample(...)` plus `order` (1 or 2), `skip_type` ("logSNR":
+    steps uniform in the log signal-to-noise ratio, snapped to the model's integer timesteps; "time_uniform": DDIM's grid) and
+    `lower_order_final` (the last step first-order).  With order=1 and skip_type="time_uniform" it is DDIM at eta = 0.  The solver is
+    deterministic: `noise` / `seed` only draw x_T (the host generator in the reference's order, or Philox).  The stages, the hand-off
+    between them, an adopted x_T, the intermediates and the callbacks are DDIM's.  What it cannot honour is refused by name."""
+    KIND = "dpm"
+
+    @torch.no_grad()
+    def sample(self, S, batch_size, shape, conditioning=None, num_stage=1, callback=None, normals_sequence=None,
+               img_callback=None, quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0.,
+               score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
+               unconditional_guidance_scale=1., unconditional_conditioning=None, noise="torch", seed=0, sample0=0,
+               replica=0, order=2, skip_type="logSNR", lower_order_final=True, **kwargs):
+        no = lambda what, why: NotImplementedError(f"DPMSolverSampler: {what} -- {why}")
+        if eta != 0:
+            raise no(f"eta={eta}", "the multistep solver integrates the probability-flow ODE; it has no stochastic (SDE) variant here")
+        if temperature != 1.:
+            raise no(f"temperature={temperature}", "no noise enters the update that it could scale")
+        if noise_dropout:
+            raise no(f"noise_dropout={noise_dropout}", "no noise enters the update that it could drop")
+        if score_corrector is not None:
+            raise no("score_corrector", "the captured step body has no hook between the denoiser and the update")
+        if mask is not None or x0 is not None:
+            raise no("mask / x0 (inpainting)", "the reference's own blend fails for multi-stage models (ddim.py:158-161), there is nothing to follow")
+        if quantize_x0:
+            raise no("quantize_x0", "the reference calls exit() on this option (ddim.py:251-253)")
+        from . import patching
+        if patching.params_of(self.model) is not None:
+            raise patching.refuse("DPMSolverSampler")
+        if isinstance(conditioning, (dict, list)) or isinstance(unconditional_conditioning, (dict, list)):
+            raise no("dict / list conditionings", "pass the cross-attention conditioning tensor or the class labels")
+        if order not in (1, 2):
+            raise ValueError(f"DPMSolverSampler: order={order!r}, the multistep solver is built for order 1 and 2")
+        if skip_type not in schedules.DPM_SKIP_TYPES:
+            raise ValueError(f"DPMSolverSampler: unknown skip_type {skip_type!r}, one of {schedules.DPM_SKIP_TYPES}")
+        ac = self.model.alphas_cumprod.detach().double().cpu().numpy()
+        self.timesteps, _ = schedules.dpm_solver_table(ac, S, skip_type, order, lower_order_final)      # a grid with no step: ValueError
+        unet = getattr(getattr(self.model, "model", None), "diffusion_model", None)
+        mode = check_conditioning(unet, conditioning, batch_size)
+        if conditioning is None:
+            if unconditional_guidance_scale != 1.:
+                raise ValueError("classifier-free guidance needs a conditioning")
+        else:
+            if unconditional_conditioning is not None and unconditional_conditioning.shape != conditioning.shape:
+                raise ValueError(f"unconditional_conditioning {tuple(unconditional_conditioning.shape)} must match "
+                                 f"conditioning {tuple(conditioning.shape)}")
+            if not conditioning.is_cuda:
+                raise FridoHipError("sample(): conditioning must live on the MI355X (there is no CPU path)")
+        if unconditional_guidance_scale != 1.:
+            assert unconditional_conditioning is not None
+        if verbose:
+            print(f"Data shape for DPM-Solver++ sampling is {(batch_size, *shape)}, order {order}, {skip_type} grid of {len(self.timesteps)} steps")
+        self.num_stage = num_stage
+        solver = (int(order), skip_type, bool(lower_order_final))
+
+        def go(noise_src):
+            eng = self._dpm_engine(batch_size, tuple(shape), mode, S, unconditional_guidance_scale, num_stage, replica, solver)
+            return eng.run(conditioning, unconditional_conditioning, x_T=x_T, noise=noise_src, seed=seed, sample0=sample0,
+                           log_every_t=log_every_t, callback=callback, img_callback=img_callback, model=self.model)
+        from . import autoplanes
+        return autoplanes.run(self.model.model.diffusion_model, go, f"{type(self).__name__}.sample", noise=noise)
+
+    def _dpm_engine(self, B, shape, nctx, S, scale, num_stage, replica, solver):
+        from .runtime import SamplerEngine
+        unet = self.model.model.diffusion_model
+        rt = unet.runtime()
+        C, H, W = shape
+        key = (self.KIND, B, C, H, W, nctx, S, scale != 1.0, num_stage, replica) + solver
+        order, skip_type, lower_order_final = solver
+        eng = cached_engine(rt, key, lambda: SamplerEngine(
+            rt.builder_for(replica), unet.cfg, B=B, C=C, H=H, W=W, nctx=nctx if isinstance(nctx, int) else 0, S=S, eta=0.0, kind=self.KIND,
+            alphas_cumprod=self.model.alphas_cumprod.detach().double().cpu().numpy(), embed_dim=self.model.embed_dim_list, cfg_scale=scale,
+            num_stage=num_stage, order=order, skip_type=skip_type, lower_order_final=lower_order_final))
+        eng.cfg_scale = float(scale)      # read from a device scalar by the captured step bodies: one graph, any scale
+        return eng

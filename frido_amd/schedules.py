@@ -108,6 +108,72 @@ def make_ddim_sampling_parameters(alphacums32, ddim_timesteps, eta):
     return sigmas, alphas, alphas_prev
 
 
+DPM_ROW = 8     # must match csrc/dpmstep.hip: inv_alpha, sigma, c_x, c_d, w_cur, w_last, pad x2
+DPM_SKIP_TYPES = ("logSNR", "time_uniform")
+
+
+def dpm_solver_grid(alphas_cumprod, S, skip_type="logSNR"):
+    """(t_loop, ac_cur, ac_next) of the DPM-Solver++ multistep loop, float64: step i evaluates the denoiser at t_loop[i] (descending) and moves
+    the state from alphas_cumprod ac_cur[i] to ac_next[i].
+    "logSNR": lambda(t) = 0.5 ln(ac_t / (1 - ac_t)); S + 1 targets uniform in lambda from lambda(T - 1) to lambda(0), each snapped to the
+    integer t with the nearest lambda (the lowest t on a tie), duplicates removed: T - 1 = t_0 > ... > t_n = 0, n <= S steps ending at ac[0].
+    "time_uniform": DDIM's grid -- make_ddim_timesteps("uniform") and the (alphas, alphas_prev) pairs of make_ddim_sampling_parameters."""
+    ac = np.asarray(alphas_cumprod, dtype=np.float64)
+    T, S = ac.shape[0], int(S)
+    if S < 1:
+        raise ValueError(f"dpm_solver_table: S = {S}, at least one step is needed")
+    if skip_type == "logSNR":
+        lam = 0.5 * np.log(ac / (1.0 - ac))
+        v = lam[T - 1] + np.arange(S + 1, dtype=np.float64) * ((lam[0] - lam[T - 1]) / S)
+        t = np.abs(lam[None, :] - v[:, None]).argmin(axis=1)      # argmin: the first (lowest) t among equals
+        t[0], t[-1] = T - 1, 0
+        grid = np.asarray(sorted(set(int(k) for k in t), reverse=True), dtype=np.int64)
+        t_loop, t_next = grid[:-1], grid[1:]
+        ac_cur, ac_next = ac[t_loop], ac[t_next]
+    elif skip_type == "time_uniform":
+        ts = make_ddim_timesteps("uniform", S, T)
+        _, al, alp = make_ddim_sampling_parameters(np.asarray(alphas_cumprod, dtype=np.float32), ts, 0.0)
+        t_loop = np.flip(ts).astype(np.int64)
+        ac_cur, ac_next = np.flip(al).astype(np.float64), np.flip(alp).astype(np.float64)
+    else:
+        raise ValueError(f"unknown skip_type {skip_type!r}: one of {DPM_SKIP_TYPES}")
+    if t_loop.shape[0] < 1:
+        raise ValueError(f"dpm_solver_table: the {skip_type} grid of S = {S} on a schedule of {T} timesteps collapses to no step")
+    return t_loop.copy(), ac_cur.copy(), ac_next.copy()
+
+
+def dpm_solver_rows(ac_cur, ac_next, order=2, lower_order_final=True):
+    """The float64 rows [n][DPM_ROW] of DPM-Solver++(2M) (Lu et al. 2022, data prediction, multistep) before rounding.  With
+    alpha = sqrt(ac_cur), sigma = sqrt(1 - ac_cur), alpha' / sigma' the same of ac_next, h = ln(alpha' / sigma') - ln(alpha / sigma) and
+    r = h_prev / h:   x' = (sigma' / sigma) x - alpha' expm1(-h) D,   D = x0 (first order) or (1 + 1 / 2r) x0 - (1 / 2r) x0_prev.
+    Row: {1 / alpha, sigma, c_x = sigma' / sigma, c_d = -alpha' expm1(-h), w_cur, w_last, 0, 0}.  First-order rows (w = 1, 0): row 0 -- every
+    stage walks the table from its top with an empty history --, every row when order = 1, the last row under lower_order_final."""
+    if order not in (1, 2):
+        raise ValueError(f"order = {order!r}: the multistep solver is built for order 1 and 2")
+    ac_cur, ac_next = np.asarray(ac_cur, dtype=np.float64), np.asarray(ac_next, dtype=np.float64)
+    n = ac_cur.shape[0]
+    a, s, a2, s2 = np.sqrt(ac_cur), np.sqrt(1.0 - ac_cur), np.sqrt(ac_next), np.sqrt(1.0 - ac_next)
+    h = np.log(a2 / s2) - np.log(a / s)
+    rows = np.zeros((n, DPM_ROW), dtype=np.float64)
+    rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3] = 1.0 / a, s, s2 / s, -a2 * np.expm1(-h)
+    rows[:, 4] = 1.0
+    for i in range(1, n):
+        if order == 1 or (lower_order_final and i == n - 1):
+            continue
+        r = h[i - 1] / h[i]
+        rows[i, 4], rows[i, 5] = 1.0 + 1.0 / (2.0 * r), -1.0 / (2.0 * r)
+    return rows
+
+
+def dpm_solver_table(alphas_cumprod, S, skip_type="logSNR", order=2, lower_order_final=True):
+    """(t_loop descending int64 [n], float32 table [n][DPM_ROW]) of the DPM-Solver++(2M) loop: dpm_solver_grid's steps, dpm_solver_rows'
+    coefficients, everything in float64 and rounded to float32 once."""
+    if order not in (1, 2):
+        raise ValueError(f"order = {order!r}: the multistep solver is built for order 1 and 2")
+    t_loop, ac_cur, ac_next = dpm_solver_grid(alphas_cumprod, S, skip_type)
+    return t_loop, dpm_solver_rows(ac_cur, ac_next, order, lower_order_final).astype(np.float32)
+
+
 def sampler_coef_table(alphacums32, S, eta, plms=False):
     """float32 table [n_steps][COEF_ROW] in LOOP order (row i = i-th executed step, index = n-1-i) plus
     the DDPM timestep of every row.  PLMS rows carry the Adams-Bashforth weights of plms.py:285-301."""

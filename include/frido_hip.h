@@ -500,6 +500,29 @@ typedef struct FridoDiffusionLoss { const float* pred; const int64_t* t; const f
 typedef struct FridoVqCommitLoss { const float* z[4]; const float* zq[4]; int64_t npix[4]; int32_t C[4], c0[4], e[4];
                                    double* partials; float* out; float* emb_loss; float beta; int32_t n_scales, legacy; } FridoVqCommitLoss;
 
+/* ---- DPM-Solver++(2M): the second-order multistep solver in data prediction (Lu et al. 2022), not in the reference ----
+ * Not an op kind: an exported launcher with a descriptor of its own (frido_dpm_step below), run eagerly or between frido_capture_begin and
+ * frido_capture_end.  One update of the NHWC f32 state x[B][HW][Cx] on the active stage channels [start, start + nch); what
+ * FridoSamplerStep carries for DDIM minus noise and PLMS history, plus x0_hist[B * HW][nch], the previous step's x0 prediction.
+ * The 8-float row coef[*step + coef_row_offset] = {inv_alpha, sigma, c_x, c_d, w_cur, w_last, pad, pad} (frido_amd/schedules.py
+ * dpm_solver_table; step NULL reads as 0).  Per active element in fp32, every product and sum rounded on its own (no contraction):
+ *   e  = eps_cond, or e_u + s (e_c - e_u) with eps_uncond, s = *cfg_dev if cfg_dev else cfg_scale   (FridoSamplerStep's expression)
+ *   x0 = (x - sigma e) inv_alpha
+ *   D  = x0 when w_last == 0 (x0_hist is then NOT read: a first-order row starts a stage on a stale history), else w_cur x0 + w_last x0_hist
+ *   x' = c_x x + c_d D;   then x0_hist <- x0
+ * Channels [0, start) pass through (x' = x, pred_x0 = x); channels from start + nch on are written in neither x_out nor pred_x0, as
+ * in FridoSamplerStep's DDIM mode.  x_out may alias x; pred_x0 is optional.  Cx, start and nch multiples of 4 and every base 16-byte
+ * aligned: 16-byte accesses; scalar accesses otherwise.  A non-finite x' raises FRIDO_STATUS_NONFINITE. */
+typedef struct FridoDpmStep {
+    float* x; int32_t B, HW, Cx, start, nch;
+    const float* eps_cond; const float* eps_uncond; float cfg_scale;   /* [B*HW][nch] */
+    const float* cfg_dev;        /* optional device float overriding cfg_scale (graph replay) */
+    const float* coef; const int32_t* step; int32_t coef_row_offset;
+    float* x_out;                /* where x' goes (may alias x) */
+    float* pred_x0;              /* optional [B][HW][Cx] */
+    float* x0_hist;              /* [B*HW][nch], read on second-order rows, always written */
+} FridoDpmStep;
+
 enum FridoOpKind {
     FRIDO_OP_GEMM = 1, FRIDO_OP_GN_STATS, FRIDO_OP_GN_APPLY, FRIDO_OP_LAYERNORM, FRIDO_OP_SOFTMAX,
     FRIDO_OP_GEGLU, FRIDO_OP_PACK, FRIDO_OP_RELAYOUT, FRIDO_OP_VQ, FRIDO_OP_SAMPLER_STEP,
@@ -592,6 +615,9 @@ int frido_diffusion_loss(const FridoDiffusionLoss* d, frido_stream_t s);
 
 /* ---- the MS-VQGAN's codebook loss (descriptor above); bad arguments return FRIDO_EINVAL before any device is touched ---- */
 int frido_vq_commit_loss(const FridoVqCommitLoss* d, frido_stream_t s);
+
+/* ---- the DPM-Solver++(2M) update (descriptor above); bad arguments return FRIDO_EINVAL before any device is touched ---- */
+int frido_dpm_step(const FridoDpmStep* d, frido_stream_t s);
 
 /* ---- timing on the launch stream (HIP events) ---- */
 int frido_event_create(void** ev);
