@@ -2,7 +2,8 @@
 
   DenoiserRuntime  — PyUNetModel.forward(x, t, context, stage) on the HIP engine (API path);
   SamplerEngine    — the multi-stage DDIM / PLMS loop with per-sample invariants hoisted, the per-step
-                     body captured in a hipGraph, a device step counter and coefficient tables
+                     body captured in a hipGraph (one builder, _body, and one replay loop, _replay over replay_units, for every
+                     kind), a device step counter and coefficient tables
                      (reference: frido/models/diffusion/ddim.py:116-273, plms.py:116-303); kind="ddpm": the
                      ancestral loop of frido/models/diffusion/frido.py:1308-1418 on the same machinery; kind="dpm":
                      DPM-Solver++(2M), which the reference does not have, in DDIM's loop (frido_dpm_step as the update);
@@ -10,21 +11,23 @@
   DecoderRuntime   — VQModelInterface.decode / decode_first_stage on the HIP engine; MSFPNVQModel's encode_quant / decode_quant /
                      reconstruct (encode program, codebook loss and decode program as one captured graph).
 """
+import contextlib
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from . import _lib, config
 from .builder import Builder
-from .engine import current_stream_ptr, require_gpu
-from .patching import FOREIGN
+from .engine import Prog, current_stream_ptr, require_gpu
+from .patching import FOREIGN, PatchProg
 from .schedules import ancestral_table, dpm_solver_table, sampler_coef_table
 from .unet_plan import UNetStagePlan
 from .vqgan_plan import VQDecodePlan, VQDecodeQuantPlan, VQEncodePlan
 
 # step bodies per captured DDIM graph (1 = one graph launch per step, the r01-r05 form; r06 default 20: 10 measured +0.17 %, 40 +0.28 % end to end, interleaved,
-# profiles/r06_graph_steps_ab.txt); see SamplerEngine._ddim_stage
+# profiles/r06_graph_steps_ab.txt); see SamplerEngine._replay
 GRAPH_STEPS = max(1, int(os.environ.get("FRIDO_GRAPH_STEPS", "20")))
 DPM_STEP = "dpm_step"
 FOREIGN[DPM_STEP] = "frido_dpm_step"      # op tag of the DPM-Solver++ update inside a step body (patching.PatchProg)
@@ -36,10 +39,17 @@ def _weights_of(module, device):
 
 def _run1(builder, kind, stream, **kw):
     """Launch a single op immediately."""
-    from .engine import Prog
     p = Prog(builder.device, builder.nsplit)
     p.emit(kind, **kw)
     p.run(stream)
+
+
+def _relayout(builder, st, src, dst, B, HW, Cn, to_nchw, c0=0, Cuse=None, Cdst=None):
+    """One NCHW <-> NHWC launch between the tensors src and dst ([B][Cn][HW] <-> [B][HW][Cn]; to_nchw: which way).  c0 / Cuse / Cdst: only
+    the channels [c0, c0 + Cuse) of src's Cn, into a dst of Cdst channels (default: all of them, into as many)."""
+    Cuse = Cn if Cuse is None else Cuse
+    _run1(builder, "FRIDO_OP_RELAYOUT", st, src=src.data_ptr(), dst=dst.data_ptr(), B=B, HW=HW, Csrc=Cn, c0=c0, Cuse=Cuse,
+          Cdst=Cuse if Cdst is None else Cdst, d0=0, to_nchw=to_nchw)
 
 
 class DenoiserRuntime:
@@ -77,8 +87,7 @@ class DenoiserRuntime:
                                             temb_rows=B, per_sample_t=True)
         plan = self.plans[key]
         xc = x.contiguous().float()
-        _run1(self.b, "FRIDO_OP_RELAYOUT", st, src=xc.data_ptr(), dst=plan.x_state.data_ptr(), B=B, HW=H * W, Csrc=Cin,
-              c0=0, Cuse=Cin, Cdst=Cin, d0=0, to_nchw=0)
+        _relayout(self.b, st, xc, plan.x_state, B, H * W, Cin, 0)
         if context is not None:
             plan.set_context(context.to(torch.float32))
         if y is not None:
@@ -87,8 +96,7 @@ class DenoiserRuntime:
         plan.pre.run(st)
         plan.step.run(st)
         out = torch.empty(B, plan.nch, H, W, dtype=torch.float32, device=self.device)
-        _run1(self.b, "FRIDO_OP_RELAYOUT", st, src=plan.eps.data_ptr(), dst=out.data_ptr(), B=B, HW=H * W, Csrc=plan.nch,
-              c0=0, Cuse=plan.nch, Cdst=plan.nch, d0=0, to_nchw=1)
+        _relayout(self.b, st, plan.eps, out, B, H * W, plan.nch, 1)
         return out
 
 
@@ -107,14 +115,12 @@ def ancestral_step(builder, x, eps, rows, coef, start, *, noise=None, temperatur
         def nhwc(t):
             t = t.contiguous().float()
             out = torch.empty(B, HW, t.shape[1], dtype=torch.float32, device=dev)
-            _run1(builder, "FRIDO_OP_RELAYOUT", st, src=t.data_ptr(), dst=out.data_ptr(), B=B, HW=HW, Csrc=t.shape[1], c0=0, Cuse=t.shape[1],
-                  Cdst=t.shape[1], d0=0, to_nchw=0)
+            _relayout(builder, st, t, out, B, HW, t.shape[1], 0)
             return out
 
         def nchw(t):
             out = torch.empty(B, Cx, H, W, dtype=torch.float32, device=dev)
-            _run1(builder, "FRIDO_OP_RELAYOUT", st, src=t.data_ptr(), dst=out.data_ptr(), B=B, HW=HW, Csrc=Cx, c0=0, Cuse=Cx, Cdst=Cx, d0=0,
-                  to_nchw=1)
+            _relayout(builder, st, t, out, B, HW, Cx, 1)
             return out
         xs, es = nhwc(x), nhwc(eps)
         ns = nhwc(noise) if noise is not None else None
@@ -132,11 +138,6 @@ def ancestral_step(builder, x, eps, rows, coef, start, *, noise=None, temperatur
                 kw.update(noise=ns.data_ptr() + off * Cx, noise_stride=0, noise_C=Cx, noise_c0=0)
             _run1(builder, "FRIDO_OP_SAMPLER_STEP", st, **kw)
         return nchw(xo), nchw(p0)
-
-
-def _relayout(builder, st, src, dst, B, HW, Cn, to_nchw):
-    _run1(builder, "FRIDO_OP_RELAYOUT", st, src=src.data_ptr(), dst=dst.data_ptr(), B=B, HW=HW, Csrc=Cn, c0=0, Cuse=Cn, Cdst=Cn, d0=0,
-          to_nchw=to_nchw)
 
 
 @torch.no_grad()
@@ -180,8 +181,30 @@ def patch_fold(builder, geo, o, B):
     return out
 
 
+def logged_at(n, log_every_t):
+    """i -> whether the result of step i of n is logged, which needs the host: the reference's `index % log_every_t == 0 or index == n - 1`
+    with index = n - 1 - i (ddim.py:177, plms.py:190; frido.py:1409 with index = t)."""
+    return lambda i: (n - 1 - i) % log_every_t == 0 or i == 0
+
+
+def replay_units(n, K, host_at):
+    """The lengths of the units n steps are replayed in.  A K-step graph exists where K > 1 and n >= K; step i starts a K-unit where one
+    exists, i + K <= n and none of the steps i ... i + K - 2 needs the host (host_at(j): its result is logged) -- a step that does may only
+    END a unit.  Every other unit is one step."""
+    units, i = [], 0
+    while i < n:
+        fits = K > 1 and n >= K and i + K <= n and not any(host_at(j) for j in range(i, i + K - 1))
+        units.append(K if fits else 1)
+        i += units[-1]
+    return units
+
+
 class SamplerEngine:
     """One instance per (denoiser weights, B, latent shape, context length, S, eta, cfg on/off, kind, patch geometry).
+
+    Every kind runs the same way: _bind_stage, then a step body ([model evaluation, _update_op, counter add], built and captured once per
+    (form, stage) by _body and kept in `graphs`) replayed by _replay in the units of replay_units.  A score corrector, an arbitrary Python
+    hook between the denoiser and the update, makes a stage run eagerly instead: forward program, _corrected_eps, update program.
 
     patch (a split_input_params dict; DDIM / PLMS only): the patch-wise mode of frido.py:1076-1152.  The state x, pred_x0, the PLMS eps
     ring, the stage hand-off and the update kernel stay on the FULL latent; the stage plans are built for the B * L crops (kh x kw) and
@@ -254,8 +277,11 @@ class SamplerEngine:
                 if self.geo is not None:
                     self.eps_full.append(torch.zeros(self.xrep * B * H * W, plan.nch, dtype=torch.float32, device=self.dev))
         self._persist = owned
-        self.graphs = {}
-        self.noise_buf = None
+        self.graphs = {}                # step bodies by (form, stage[, "x<K>"]): captured graphs, or (use_graph=False) the programs themselves
+        self.graph_captures = 0         # bodies built
+        self.multi_step_launches = 0    # K-step units replayed (tests: the K-step graph really ran)
+        self._last_logged_stage = None
+        self._tape_bufs = {}            # DDIM host noise: the stage's whole tape [n][B][H][W][Cs], at a fixed address
         self._stream = None
         # PLMS state
         if kind == "plms":
@@ -274,26 +300,28 @@ class SamplerEngine:
             self.coef_c = torch.zeros(self.unit, tab.shape[1], dtype=torch.float32, device=self.dev)
             self.tape = None
 
-    # ---- helpers ---------------------------------------------------------------------------------
-    def _stream_ptr(self):
-        if self._stream is None:
-            self._stream = torch.cuda.Stream(device=self.dev)
-        return self._stream
-
+    # ---- the parts of a step body ------------------------------------------------------------------
     def _step_add(self, prog, delta):
         """Advance the device step counter (and, for a class-conditional denoiser, the per-sample table counter by delta * Bx)."""
         prog.emit("FRIDO_OP_STEP_ADD", step=self.step.data_ptr(), delta=delta)
         if self.labels:
             prog.emit("FRIDO_OP_STEP_ADD", step=self.step_bx.data_ptr(), delta=delta * self.Bm * self.xrep)
 
-    def _prog(self):
-        """An empty program for a step body: in patch mode one whose op list may hold the unfold / fold launches, for the DPM solver
-        one that may hold its update (an exported launcher too, not an op kind)."""
-        if self.geo is not None or self.kind == "dpm":
-            from .patching import PatchProg
-            return PatchProg(self.dev, self.b.nsplit)
-        from .engine import Prog
-        return Prog(self.dev, self.b.nsplit)
+    def _prog(self, ops=()):
+        """A program for a step body -- in patch mode one whose op list may hold the unfold / fold launches, for the DPM solver one that may
+        hold its update (an exported launcher too, not an op kind) -- filled from `ops`: a (tag, descriptor) pair is one op, a list holds
+        finished ops (a model evaluation: _eval_ops), an int advances the step counter."""
+        p = PatchProg(self.dev, self.b.nsplit) if self.geo is not None or self.kind == "dpm" else Prog(self.dev, self.b.nsplit)
+        for op in ops:
+            if isinstance(op, int):
+                self._step_add(p, op)
+            elif isinstance(op, list):
+                p.ops += op
+            elif op[0] in FOREIGN:
+                p.ops.append(op)
+            else:
+                p.emit(op[0], **op[1])
+        return p
 
     def _eval_ops(self, s):
         """The ops of ONE model evaluation at stage s, leaving eps where _eps_ptr(s) points."""
@@ -307,63 +335,162 @@ class SamplerEngine:
     def _eps_ptr(self, s):
         return (self.eps_full[s] if self.geo is not None else self.stages[s].eps).data_ptr()
 
-    def _run_pre(self, plan, sp):
-        if self.geo is not None:
-            from .patching import launch_unfold
-            launch_unfold(self.unfold_x, sp)
-        plan.pre.run(sp)
+    def _update_op(self, s, noise=None, hist_mode=0, no_cfg=False):
+        """(op tag, descriptor) of stage s's state update on the engine's buffers, for its kind: the DDIM / PLMS step (hist_mode: how PLMS uses
+        its eps ring), the ancestral step, or (DPM_STEP, FridoDpmStep) with the stage's x0 history.  noise: None -- Philox in the kernel, keyed
+        by the device {seed, sample0} -- or (address, channels) of host noise [step][B][HW][channels] read by step index.  no_cfg: the eps is
+        already guidance-mixed (a score corrector ran)."""
+        B, HW, C = self.B, self.H * self.W, self.C
+        start, nch, eps = sum(self.embed[:s]), self.embed[s], self._eps_ptr(s)
+        kw = dict(x=self.x.data_ptr(), B=B, HW=HW, Cx=C, start=start, nch=nch, eps_cond=eps, coef=self.coef.data_ptr(),
+                  step=self.step.data_ptr(), x_out=self.x.data_ptr(), pred_x0=self.pred_x0.data_ptr())
+        if self.kind != "ddpm":
+            kw.update(cfg_scale=self.cfg_scale, cfg_dev=self.cfg_dev.data_ptr())
+            if self.xrep == 2 and not no_cfg:
+                kw["eps_uncond"] = eps + 4 * B * HW * nch
+        if self.kind == "dpm":
+            return DPM_STEP, _lib.STRUCTS["FridoDpmStep"](x0_hist=self.x0_hist[s].data_ptr(), **kw)
+        kw.update(write_x=1, temperature=self.temperature, rng_stream=s + 1, rng_dev=self.rng.data_ptr())
+        if noise is not None:
+            kw.update(noise=noise[0], noise_stride=B * HW * noise[1], noise_C=noise[1], noise_c0=start)
+        if self.kind == "ddpm":
+            kw["hist_mode"] = _lib.STEP_ANCESTRAL
+            if noise is None:
+                kw["coef_row_offset"] = self.row0
+            else:     # this unit's noise (already multiplied by its temperature) and coefficient rows, by the unit's own counter
+                del kw["rng_stream"], kw["rng_dev"]
+                kw.update(coef=self.coef_c.data_ptr(), step=self.step_c.data_ptr(), temperature=1.0, noise_c0=0)
+        elif hist_mode:
+            kw.update(hist_ring=self.hist.data_ptr(), hist_stride=self.hist_stride, hist_mode=hist_mode)
+        return "FRIDO_OP_SAMPLER_STEP", kw
+
+    def _body(self, key, sp, build_ops):
+        """The step body kept under `key` = (form, stage[, "x<K>"]), built on first use from build_ops(): captured, or (use_graph=False) the
+        program itself."""
+        if key not in self.graphs:
+            p = self._prog(build_ops())
+            p.keep = [self.stages[key[1]]]
+            self.graphs[key] = p.capture(sp) if self.use_graph else p
+            self.graph_captures += 1
+        return self.graphs[key]
+
+    def _go(self, g, sp):
+        g.launch(sp) if self.use_graph else g.run(sp)
+
+    def _replay(self, key, K, host_at, sp, before_unit=None, after_unit=None, first=None):
+        """All n steps of a stage from the body under `key`, in the units of replay_units.  K > 1: the same body K times in ONE captured graph
+        (the device step counter makes every repetition pick its own timestep / noise slice), replayed wherever the K - 1 steps in between need
+        no host access: fewer graph launches -- the trace shows ~30 us between the last kernel of one replay and the first of the next
+        (profiles/r05_x3_gap_analysis.json).  before_unit(i, length) / after_unit(last step) are the kind's host work around a unit; `first`:
+        the body of step 0 where it differs (PLMS)."""
+        n, g = self.n_steps, self.graphs[key]
+        # (Graph.keep = (packed descriptor array, the program it was captured from))
+        gk = self._body(key + ("x%d" % K,), sp, lambda: [list(g.keep[1].ops) * K]) if K > 1 and n >= K else None
+        i = 0
+        for unit in replay_units(n, K, host_at):
+            if before_unit is not None:
+                before_unit(i, unit)
+            if unit > 1:
+                self._go(gk, sp)
+                self.multi_step_launches += 1
+            else:
+                self._go(first if first is not None and i == 0 else g, sp)
+            i += unit
+            after_unit(i - 1)
+
+    # ---- what a run and a stage start with ----------------------------------------------------------
+    @staticmethod
+    def _host_draw(noise):
+        """shape -> tensor for the host-noise forms ("torch": torch's global CPU generator; a callable: a recorded tape), None for "philox"."""
+        return (lambda shape: torch.randn(shape)) if noise == "torch" else (noise if callable(noise) else None)
+
+    def _context(self, cond, uncond=None):
+        """cond on the device: the cross-attention context (SpatialTransformer denoisers), class labels (class-conditional ones) or None;
+        under classifier-free guidance [cond | uncond]."""
+        ctx = cond.to(self.dev, torch.float32 if not self.labels or cond.is_floating_point() else torch.int64) if cond is not None else None
+        if self.xrep == 2:
+            assert ctx is not None, "classifier-free guidance needs a conditioning"
+            ctx = torch.cat([ctx, uncond.to(self.dev, ctx.dtype)], dim=0)
+        return ctx
+
+    def _init_x(self, x_T, draw, seed, sample0, sp):
+        """The start of the chain (ddim.py:127-130): the given x_T, a host draw, or Philox on the device."""
+        B, C, H, W = self.B, self.C, self.H, self.W
+        xt = x_T if x_T is not None else draw((B, C, H, W)) if draw is not None else None
+        if xt is not None:
+            xd = torch.as_tensor(xt, dtype=torch.float32).to(self.dev).contiguous()
+            assert xd.shape == (B, C, H, W), (tuple(xd.shape), (B, C, H, W))
+            _relayout(self.b, sp, xd, self.x, B, H * W, C, 0)
+        else:
+            _run1(self.b, "FRIDO_OP_RANDN", sp, dst=self.x.data_ptr(), n=B * H * W * C, per_sample=H * W * C, seed=seed, sample0=sample0,
+                  rng_stream=0)
 
     def _per_crop(self, t):
         """A per-sample input of the model ([xrep * B, ...]) repeated for its L crops (crop l of sample b is entry b * L + l)."""
         return t.repeat_interleave(self.geo.L, dim=0) if self.geo is not None and t is not None else t
 
-    def _sampler_op(self, s, *, noise_ptr, noise_C, seed, sample0, write_x=1, x_out=None, eps_out=None, hist=(),
-                    row_offset=0, hist_mode=0, no_cfg=False):
+    def _bind_stage(self, s, ctx, t_loop, sp):
+        """Stage s's plan on this run's conditioning and timesteps, the step counters at 0, the per-sample invariants (`pre`) computed."""
         plan = self.stages[s]
-        start = sum(self.embed[:s])
-        nch = self.embed[s]
-        BHW = self.B * self.H * self.W
-        kw = dict(x=self.x.data_ptr(), B=self.B, HW=self.H * self.W, Cx=self.C, start=start, nch=nch,
-                  eps_cond=self._eps_ptr(s), cfg_scale=self.cfg_scale, coef=self.coef.data_ptr(),
-                  step=self.step.data_ptr(), coef_row_offset=row_offset, temperature=self.temperature,
-                  x_out=(x_out if x_out is not None else self.x.data_ptr()), pred_x0=self.pred_x0.data_ptr(),
-                  write_x=write_x, seed=seed, sample0=sample0, rng_stream=s + 1, rng_dev=self.rng.data_ptr(),
-                  cfg_dev=self.cfg_dev.data_ptr())
-        if hist_mode:
-            kw.update(hist_ring=self.hist.data_ptr(), hist_stride=self.hist_stride, hist_mode=hist_mode)
-        if self.xrep == 2 and not no_cfg:
-            kw["eps_uncond"] = self._eps_ptr(s) + 4 * BHW * nch
-        if noise_ptr:
-            kw.update(noise=noise_ptr, noise_stride=BHW * noise_C, noise_C=noise_C, noise_c0=start)
-        if eps_out is not None:
-            kw["eps_out"] = eps_out
-        for i, h in enumerate(hist):
-            kw[f"hist{i + 1}"] = h
-        return kw
+        if self.labels:
+            plan.set_labels(self._per_crop(ctx))
+        elif ctx is not None:
+            plan.set_context(self._per_crop(ctx))
+        plan.set_timesteps(t_loop)
+        self.step.zero_()
+        if self.labels:
+            self.step_bx.zero_()
+        if self.geo is not None:
+            from .patching import launch_unfold
+            launch_unfold(self.unfold_x, sp)
+        plan.pre.run(sp)
 
-    def _dpm_desc(self, s):
-        """FridoDpmStep of stage s on the engine's state: what _sampler_op gives the DDIM update, and the stage's x0 history."""
-        start, nch = sum(self.embed[:s]), self.embed[s]
-        BHW = self.B * self.H * self.W
-        return _lib.STRUCTS["FridoDpmStep"](
-            x=self.x.data_ptr(), B=self.B, HW=self.H * self.W, Cx=self.C, start=start, nch=nch, eps_cond=self._eps_ptr(s),
-            eps_uncond=self._eps_ptr(s) + 4 * BHW * nch if self.xrep == 2 else None, cfg_scale=self.cfg_scale, cfg_dev=self.cfg_dev.data_ptr(),
-            coef=self.coef.data_ptr(), step=self.step.data_ptr(), coef_row_offset=0, x_out=self.x.data_ptr(), pred_x0=self.pred_x0.data_ptr(),
-            x0_hist=self.x0_hist[s].data_ptr())
+    @contextlib.contextmanager
+    def _own_stream(self):
+        """The engine's stream, ordered after the caller's on entry and before it on exit; yields its handle."""
+        if self._stream is None:
+            self._stream = torch.cuda.Stream(device=self.dev)
+        self._stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(self._stream):
+            yield self._stream.cuda_stream
+        torch.cuda.current_stream(self.dev).wait_stream(self._stream)
+
+    def _to_nchw(self, nhwc, sp):
+        out = torch.empty(self.B, nhwc.shape[-1], self.H, self.W, dtype=torch.float32, device=self.dev)
+        _relayout(self.b, sp, nhwc, out, self.B, self.H * self.W, nhwc.shape[-1], 1)
+        return out
 
     def _upload_noise(self, s, tape):
-        """tape: list of per-step NCHW tensors (B, 3(s+1), H, W) in draw order -> the stage's persistent NHWC device buffer
-        (fixed address: the captured step body of the tape mode reads it by step index)."""
+        """tape: list of per-step NCHW tensors (B, 3(s+1), H, W) in draw order -> (address, channels) of the stage's persistent NHWC device
+        buffer (fixed address: the captured step body of the tape mode reads it by step index)."""
         Cs = sum(self.embed[:s + 1])
         t = torch.stack([torch.as_tensor(n, dtype=torch.float32) for n in tape])     # [n][B][Cs][H][W]
         assert t.shape[1:] == (self.B, Cs, self.H, self.W), (t.shape, Cs)
-        bufs = self.__dict__.setdefault("_tape_bufs", {})
-        if s not in bufs:
-            bufs[s] = torch.empty(t.shape[0], self.B, self.H, self.W, Cs, dtype=torch.float32, device=self.dev)
-        bufs[s].copy_(t.permute(0, 1, 3, 4, 2), non_blocking=False)                 # plumbing: layout + H2D
-        return bufs[s].data_ptr(), Cs
+        if s not in self._tape_bufs:
+            self._tape_bufs[s] = torch.empty(t.shape[0], self.B, self.H, self.W, Cs, dtype=torch.float32, device=self.dev)
+        self._tape_bufs[s].copy_(t.permute(0, 1, 3, 4, 2), non_blocking=False)      # plumbing: layout + H2D
+        return self._tape_bufs[s].data_ptr(), Cs
 
-    # ---- main entry --------------------------------------------------------------------------------
+    def _corrected_eps(self, s, sp, t_value, o):
+        """`score_corrector.modify_score(model, e_t, x, t, c, **kwargs)` (ddim.py:228-230, plms.py:236-238, frido.py:1233-1241) on the eps the
+        forward program just wrote: CFG mix (ddim.py:226), zero-padded like the reference's e_t -- to the channels reached so far, in the
+        ancestral loop to the latent's -- hook on torch tensors (NCHW), the stage's channels written back as the (already mixed) conditional
+        eps the update kernel reads."""
+        plan = self.stages[s]
+        B, H, W = self.B, self.H, self.W
+        start, nch = sum(self.embed[:s]), self.embed[s]
+        Cp = self.C if self.kind == "ddpm" else start + nch
+        e = plan.eps.view(self.xrep, B, H, W, nch).permute(0, 1, 4, 2, 3)            # [cond | uncond] x (B, nch, H, W)
+        e_t = e[0] if self.xrep == 1 else e[1] + self.cfg_scale * (e[0] - e[1])
+        e_t = torch.cat((torch.zeros(B, start, H, W, device=self.dev), e_t, torch.zeros(B, Cp - start - nch, H, W, device=self.dev)), dim=1)
+        x_now = self._to_nchw(self.x, sp)[:, :Cp]
+        t = torch.full((B,), int(t_value), device=self.dev, dtype=torch.long)
+        e_new = o.score_corrector.modify_score(o.model, e_t, x_now, t, o.cond, **o.corrector_kwargs)
+        e_new = e_new.to(torch.float32).contiguous()
+        assert e_new.shape == (B, Cp, H, W), "modify_score must return a tensor of e_t's shape"
+        _relayout(self.b, sp, e_new, plan.eps, B, H * W, Cp, 0, c0=start, Cuse=nch, Cdst=nch)
+
+    # ---- DDIM / PLMS / DPM-Solver++ ----------------------------------------------------------------
     @torch.no_grad()
     @_lib.with_planes
     def run(self, cond, uncond=None, *, x_T=None, noise="philox", seed=0, sample0=0, log_every_t=100, callback=None,
@@ -375,316 +502,127 @@ class SamplerEngine:
         stage x_T comes back unchanged).
         noise_dropout (ddim.py:260-262; plms.py get_x_prev_and_pred_x0): F.dropout of the update's noise -- its keep mask comes from
         torch's generator right after the randn, so it exists in the host-noise modes only ("torch" / a tape).
-        score_corrector (ddim.py:228-230): an arbitrary Python hook between the denoiser and the update -- the DDIM stage then runs
+        score_corrector (ddim.py:228-230): an arbitrary Python hook between the denoiser and the update -- a stage then runs
         step by step on the stream (forward program, hook on torch tensors, update kernel) instead of replaying a captured graph.
         Returns (samples NCHW, intermediates dict)."""
-        B, C, H, W = self.B, self.C, self.H, self.W
         assert self.kind != "ddpm", "an ancestral engine runs through run_ancestral()"
         if self.kind == "dpm" and (noise_dropout > 0. or score_corrector is not None):
             raise NotImplementedError("the DPM-Solver loop is deterministic and has no hook between the denoiser and the update: "
                                       "noise_dropout / score_corrector are not built for it")
-        self._opts = dict(noise_dropout=float(noise_dropout), score_corrector=score_corrector, corrector_kwargs=dict(corrector_kwargs or {}),
-                          model=model, cond=cond, uncond=uncond)
         if noise_dropout > 0. and noise == "philox":
             raise NotImplementedError("noise_dropout draws its keep mask from torch's generator: use noise='torch' (or a recorded tape)")
         if score_corrector is not None and self.geo is not None:
             from .patching import refuse
             raise refuse("score_corrector")
-        stream = self._stream_ptr()
-        stream.wait_stream(torch.cuda.current_stream(self.dev))
-        sp = stream.cuda_stream
-        draw = None
-        if noise == "torch":
-            draw = lambda shape: torch.randn(shape)
-        elif callable(noise):
-            draw = noise
-        with torch.cuda.stream(stream):
-            # cond: the cross-attention context (SpatialTransformer denoisers), class labels (class-conditional ones) or None
-            ctx = cond.to(self.dev, torch.float32 if not self.labels or cond.is_floating_point() else torch.int64) if cond is not None else None
-            if self.xrep == 2:
-                assert ctx is not None, "classifier-free guidance needs a conditioning"
-                ctx = torch.cat([ctx, uncond.to(self.dev, ctx.dtype)], dim=0)
+        o = SimpleNamespace(draw=self._host_draw(noise), seed=seed, sample0=sample0, log_every_t=log_every_t, callback=callback,
+                            img_callback=img_callback, noise_dropout=float(noise_dropout), score_corrector=score_corrector,
+                            corrector_kwargs=dict(corrector_kwargs or {}), model=model, cond=cond, temps=None)
+        with self._own_stream() as sp:
+            ctx = self._context(cond, uncond)
             self.cfg_dev.fill_(self.cfg_scale)
-            # ---- x_T (ddim.py:127-130) ----
-            if x_T is not None:
-                xt = torch.as_tensor(x_T, dtype=torch.float32)
-            elif draw is not None:
-                xt = draw((B, C, H, W))
-            else:
-                xt = None
-            if xt is not None:
-                xd = xt.to(self.dev).contiguous()
-                _run1(self.b, "FRIDO_OP_RELAYOUT", sp, src=xd.data_ptr(), dst=self.x.data_ptr(), B=B, HW=H * W, Csrc=C,
-                      c0=0, Cuse=C, Cdst=C, d0=0, to_nchw=0)
-            else:
-                _run1(self.b, "FRIDO_OP_RANDN", sp, dst=self.x.data_ptr(), n=B * H * W * C, per_sample=H * W * C, seed=seed,
-                      sample0=sample0, rng_stream=0)
+            self._init_x(x_T, o.draw, seed, sample0, sp)
             x0_nchw = self._to_nchw(self.x, sp)
-            inter = {"x_inter": [x0_nchw], "pred_x0": [x0_nchw]}
+            o.inter = {"x_inter": [x0_nchw], "pred_x0": [x0_nchw]}
             t_loop = torch.from_numpy(self.t_loop.astype(np.int64)).to(self.dev)
-            n = self.n_steps
             for s in range(self.num_stage):
                 if x_T is not None and s == 0:
                     continue                 # ddim.py:150-152: "Auto adopt x_T into stage 0" (no denoising, no hand-off)
-                plan = self.stages[s]
-                Cs = sum(self.embed[:s + 1])
-                if self.labels:
-                    plan.set_labels(self._per_crop(ctx))
-                elif ctx is not None:
-                    plan.set_context(self._per_crop(ctx))
-                plan.set_timesteps(t_loop)
-                self.step.zero_()
-                if self.labels:
-                    self.step_bx.zero_()
-                self._run_pre(plan, sp)
-                if self.kind in ("ddim", "dpm"):
-                    self._ddim_stage(s, sp, draw, seed, sample0, inter, log_every_t, callback, img_callback, Cs)
-                else:
-                    self._plms_stage(s, sp, draw, seed, sample0, inter, log_every_t, callback, img_callback, Cs)
-                if self.num_stage != 1:
-                    levels = self.num_stage - s - 1
-                    if levels > 0:
-                        c0, c1 = sum(self.embed[:s]), sum(self.embed[:s + 1])
-                        _run1(self.b, "FRIDO_OP_HANDOFF", sp, x=self.x.data_ptr(), B=B, H=H, W=W, Cx=C, c0=c0, c1=c1,
-                              levels=levels)
-                        # the reference mutates the logged tensor in place (ddim.py:185): mirror that
-                        if inter["x_inter"] and getattr(self, "_last_logged_stage", None) == s:
-                            inter["x_inter"][-1] = self._to_nchw(self.x, sp)[:, :Cs]
+                self._bind_stage(s, ctx, t_loop, sp)
+                (self._plms_stage if self.kind == "plms" else self._ddim_stage)(s, sp, o)
+                levels = self.num_stage - s - 1
+                if levels > 0:
+                    c0, c1 = sum(self.embed[:s]), sum(self.embed[:s + 1])
+                    _run1(self.b, "FRIDO_OP_HANDOFF", sp, x=self.x.data_ptr(), B=self.B, H=self.H, W=self.W, Cx=self.C, c0=c0, c1=c1,
+                          levels=levels)
+                    # the reference mutates the logged tensor in place (ddim.py:185): mirror that
+                    if o.inter["x_inter"] and self._last_logged_stage == s:
+                        o.inter["x_inter"][-1] = self._to_nchw(self.x, sp)[:, :c1]
             out = self._to_nchw(self.x, sp)
-        torch.cuda.current_stream(self.dev).wait_stream(stream)
-        return out, inter
+        return out, o.inter
 
-    def _to_nchw(self, nhwc, sp):
-        B, H, W = self.B, self.H, self.W
-        C = nhwc.shape[-1]
-        out = torch.empty(B, C, H, W, dtype=torch.float32, device=self.dev)
-        _run1(self.b, "FRIDO_OP_RELAYOUT", sp, src=nhwc.data_ptr(), dst=out.data_ptr(), B=B, HW=H * W, Csrc=C, c0=0,
-              Cuse=C, Cdst=C, d0=0, to_nchw=1)
-        return out
-
-    def _log(self, s, i, inter, log_every_t, sp, Cs, callback, img_callback):
-        n = self.n_steps
-        index = n - i - 1
-        if callback:
-            callback(i)
-        if img_callback:
-            img_callback(self._to_nchw(self.pred_x0, sp)[:, :Cs], i)
-        if index % log_every_t == 0 or index == n - 1:
-            inter["x_inter"].append(self._to_nchw(self.x, sp)[:, :Cs])
-            inter["pred_x0"].append(self._to_nchw(self.pred_x0, sp)[:, :Cs])
+    def _log(self, s, i, sp, o):
+        n, Cs = self.n_steps, sum(self.embed[:s + 1])
+        if o.callback:
+            o.callback(i)
+        if o.img_callback:
+            o.img_callback(self._to_nchw(self.pred_x0, sp)[:, :Cs], i)
+        if logged_at(n, o.log_every_t)(i):
+            o.inter["x_inter"].append(self._to_nchw(self.x, sp)[:, :Cs])
+            o.inter["pred_x0"].append(self._to_nchw(self.pred_x0, sp)[:, :Cs])
             self._last_logged_stage = s if i == n - 1 else None
 
-    def _ddim_stage(self, s, sp, draw, seed, sample0, inter, log_every_t, callback, img_callback, Cs):
-        """ddim.py:155-175.  ONE captured hipGraph per stage (denoiser forward + state update + step-counter bump) is
-        replayed every step: the Philox form draws its noise in the update kernel, the tape form (recorded / torch-CPU noise)
-        reads the stage's persistent noise buffer by step index."""
-        from .engine import Prog
-        plan = self.stages[s]
-        n = self.n_steps
-        opts = getattr(self, "_opts", {})
-        p_drop = opts.get("noise_dropout", 0.0)
-        if draw is not None and p_drop > 0.:
-            base = draw
-            # dropout(sigma * noise * temperature) = sigma * temperature * dropout(noise): applied to the host tape, mask drawn right
-            # after the step's randn like the reference does
-            draw = lambda shape: torch.nn.functional.dropout(base(shape), p=p_drop)
-        if opts.get("score_corrector") is not None:
-            return self._ddim_stage_with_corrector(s, sp, draw, seed, sample0, inter, log_every_t, callback, img_callback, Cs, opts)
-        if self.kind == "dpm":
-            # DPM-Solver++(2M): no noise after x_T (the host generator is left alone); the body is model evaluation, frido_dpm_step, counter add
-            key = ("dpm", s)
-            if key not in self.graphs:
-                body = self._prog()
-                body.ops = self._eval_ops(s) + [(DPM_STEP, self._dpm_desc(s))]
-                self._step_add(body, 1)
-                body.keep = [plan]
-                self.graphs[key] = body.capture(sp) if self.use_graph else body
-            g = self.graphs[key]
-            launch = (lambda: g.launch(sp)) if self.use_graph else (lambda: g.run(sp))
-        elif draw is not None:
-            noise_ptr, noise_C = self._upload_noise(s, [draw((self.B, Cs, self.H, self.W)) for _ in range(n)])
-            key = ("ddim_tape", s)
-            if key not in self.graphs:
-                body = self._prog()
-                body.ops = self._eval_ops(s)
-                body.emit("FRIDO_OP_SAMPLER_STEP", **self._sampler_op(s, noise_ptr=noise_ptr, noise_C=noise_C, seed=0, sample0=0))
-                self._step_add(body, 1)
-                body.keep = [plan]
-                self.graphs[key] = body.capture(sp) if self.use_graph else body
-            g = self.graphs[key]
-            launch = (lambda: g.launch(sp)) if self.use_graph else (lambda: g.run(sp))
-        else:
-            self.rng.copy_(torch.tensor([seed, sample0], dtype=torch.int64))
-            key = ("ddim", s)
-            if key not in self.graphs:
-                full = self._prog()
-                full.ops = self._eval_ops(s)
-                full.emit("FRIDO_OP_SAMPLER_STEP", **self._sampler_op(s, noise_ptr=None, noise_C=0, seed=0, sample0=0))
-                self._step_add(full, 1)
-                full.keep = [plan]
-                self.graphs[key] = full.capture(sp) if self.use_graph else full
-            g = self.graphs[key]
-            launch = (lambda: g.launch(sp)) if self.use_graph else (lambda: g.run(sp))
-        # (r06) GRAPH_STEPS > 1: the same step body K times in ONE captured graph (the device step counter makes every repetition pick its own
-        # timestep / noise slice), replayed wherever the K - 1 steps in between need no host access (log / callbacks): fewer graph launches --
-        # the trace shows ~30 us between the last kernel of one replay and the first of the next (profiles/r05_x3_gap_analysis.json)
-        K = GRAPH_STEPS if self.use_graph else 1
-        gk = None
-        if K > 1 and n >= K and callback is None and img_callback is None:
-            kkey = key + ("x%d" % K,)
-            if kkey not in self.graphs:
-                multi = self._prog()
-                multi.ops = list(g.keep[1].ops) * K          # (Graph.keep = (packed descriptor array, the Prog it was captured from))
-                multi.keep = [plan]
-                self.graphs[kkey] = multi.capture(sp)
-            gk = self.graphs[kkey]
-        needs_host = lambda i: (n - i - 1) % log_every_t == 0 or i == 0              # when _log touches the state at step i (index = n - i - 1) without callbacks
-        i = 0
-        while i < n:
-            if gk is not None and i + K <= n and not any(needs_host(j) for j in range(i, i + K - 1)):
-                gk.launch(sp)
-                self.multi_step_launches = getattr(self, "multi_step_launches", 0) + 1      # (tests: the K-step graph really ran)
-                i += K
-            else:
-                launch()
-                i += 1
-            self._log(s, i - 1, inter, log_every_t, sp, Cs, callback, img_callback)
+    def _unit_steps(self, o, K):
+        """Steps per replay unit: callbacks want the host after every step, and only captured bodies are chained."""
+        return K if self.use_graph and o.callback is None and o.img_callback is None else 1
 
-    def _corrected_eps(self, s, sp, Cs, t_value, opts):
-        """`score_corrector.modify_score(model, e_t, x, t, c, **kwargs)` (ddim.py:228-230, plms.py:236-238) on the eps the forward
-        program just wrote: CFG mix (ddim.py:226), frozen channels zero-padded like the reference's e_t, hook on torch tensors
-        (NCHW), active channels written back as the (already mixed) conditional eps the update kernel reads."""
-        plan = self.stages[s]
-        B, H, W = self.B, self.H, self.W
-        start, nch = sum(self.embed[:s]), self.embed[s]
-        e = plan.eps.view(self.xrep, B, H, W, nch).permute(0, 1, 4, 2, 3)            # [cond | uncond] x (B, nch, H, W)
-        e_t = e[0]
-        if self.xrep == 2:
-            e_t = e[1] + self.cfg_scale * (e_t - e[1])
-        e_t = torch.cat((torch.zeros(B, start, H, W, device=self.dev), e_t), dim=1) if start else e_t.contiguous()
-        x_now = self._to_nchw(self.x, sp)[:, :Cs]
-        t = torch.full((B,), int(t_value), device=self.dev, dtype=torch.long)
-        e_new = opts["score_corrector"].modify_score(opts["model"], e_t, x_now, t, opts["cond"], **opts["corrector_kwargs"])
-        e_new = e_new.to(torch.float32).contiguous()
-        assert e_new.shape == (B, Cs, H, W), "modify_score must return a tensor of e_t's shape"
-        _run1(self.b, "FRIDO_OP_RELAYOUT", sp, src=e_new.data_ptr(), dst=plan.eps.data_ptr(), B=B, HW=H * W, Csrc=Cs, c0=start,
-              Cuse=nch, Cdst=nch, d0=0, to_nchw=0)
+    def _ddim_stage(self, s, sp, o):
+        """ddim.py:155-175.  ONE step body per stage (denoiser forward + state update + step-counter bump) is replayed every step: the
+        Philox form draws its noise in the update kernel, the tape form (recorded / torch-CPU noise) reads the stage's persistent noise
+        buffer by step index.  DPM-Solver++(2M): no noise after x_T (the host generator is left alone), frido_dpm_step as the update."""
+        plan, n, noise = self.stages[s], self.n_steps, None
+        if self.kind == "ddim" and o.draw is not None:
+            # dropout(sigma * noise * temperature) = sigma * temperature * dropout(noise): applied to the host tape, mask drawn right after
+            # the step's randn like the reference does
+            drop = (lambda z: torch.nn.functional.dropout(z, p=o.noise_dropout)) if o.noise_dropout > 0. else (lambda z: z)
+            noise = self._upload_noise(s, [drop(o.draw((self.B, sum(self.embed[:s + 1]), self.H, self.W))) for _ in range(n)])
+        elif self.kind == "ddim":
+            self.rng.copy_(torch.tensor([o.seed, o.sample0], dtype=torch.int64))
+        log = lambda i: self._log(s, i, sp, o)
+        if o.score_corrector is not None:       # ddim.py:188-273 with the hook between the (CFG-mixed) eps and the update
+            upd = self._prog([self._update_op(s, noise, no_cfg=True), 1])
+            for i in range(n):
+                plan.step.run(sp)
+                self._corrected_eps(s, sp, self.t_loop[i], o)
+                upd.run(sp)
+                log(i)
+            return
+        key = ("dpm" if self.kind == "dpm" else "ddim_tape" if noise else "ddim", s)
+        self._body(key, sp, lambda: [self._eval_ops(s), self._update_op(s, noise), 1])
+        self._replay(key, self._unit_steps(o, GRAPH_STEPS), logged_at(n, o.log_every_t), sp, after_unit=log)
 
-    def _ddim_stage_with_corrector(self, s, sp, draw, seed, sample0, inter, log_every_t, callback, img_callback, Cs, opts):
-        """ddim.py:188-273 with the score corrector between the (CFG-mixed) eps and the update: eager, one step at a time --
-        forward program, hook, update kernel."""
-        from .engine import Prog
-        plan = self.stages[s]
-        n, B, H, W = self.n_steps, self.B, self.H, self.W
-        if draw is not None:
-            noise_ptr, noise_C = self._upload_noise(s, [draw((B, Cs, H, W)) for _ in range(n)])
-        else:
-            noise_ptr, noise_C = None, 0
-            self.rng.copy_(torch.tensor([seed, sample0], dtype=torch.int64))
-        upd = Prog(self.dev, self.b.nsplit)
-        upd.emit("FRIDO_OP_SAMPLER_STEP", **self._sampler_op(s, noise_ptr=noise_ptr, noise_C=noise_C, seed=0, sample0=0, no_cfg=True))
-        self._step_add(upd, 1)
-        t_steps = self.t_loop.astype(np.int64)
-        for i in range(n):
-            plan.step.run(sp)
-            self._corrected_eps(s, sp, Cs, t_steps[i], opts)
-            upd.run(sp)
-            self._log(s, i, inter, log_every_t, sp, Cs, callback, img_callback)
-
-    def _plms_stage_with_corrector(self, s, sp, draw, seed, sample0, inter, log_every_t, callback, img_callback, Cs, opts):
-        """plms.py:156-194,198-303 with the score corrector inside every model evaluation (plms.py:236-238): the op sequences of
-        the two captured PLMS programs, run eagerly with the hook after each forward.  The corrected eps is what enters the
-        Adams-Bashforth history ring (plms.py:175-177 appends get_model_output's result)."""
-        from .engine import Prog
-        plan = self.stages[s]
-        n = self.n_steps
-        self.rng.copy_(torch.tensor([seed, sample0], dtype=torch.int64))
+    def _plms_stage(self, s, sp, o):
+        """plms.py:156-194,285-303: Heun-style first step (two denoiser calls), then Adams-Bashforth 2/3/4.  Two step bodies per stage serve
+        every step: `first` = [forward, save x, update with e_t (eps -> ring slot 0), step+1, forward at (x_prev, t_next), step-1, restore x,
+        update with (e_t + e_next)/2, step+1]; `body` = [forward, update with the ring history selected by the device step counter, step+1].
+        eta == 0 (plms.py:25-26), so no noise enters the update and the same bodies serve the philox / torch / tape modes.
+        With a score corrector (plms.py:236-238, inside every model evaluation) the same op sequences run eagerly with the hook after each
+        forward; the corrected eps is what enters the history ring (plms.py:175-177 appends get_model_output's result)."""
+        plan, n = self.stages[s], self.n_steps
+        self.rng.copy_(torch.tensor([o.seed, o.sample0], dtype=torch.int64))
         nbytes = self.x.numel() * 4
-
-        def prog(*ops):
-            p = Prog(self.dev, self.b.nsplit)
-            for kind, kw in ops:
-                if kind == "step_add":
-                    self._step_add(p, kw)
-                else:
-                    p.emit(kind, **kw)
-            return p
-        step_add = lambda d: ("step_add", d)
-        upd = lambda mode: ("FRIDO_OP_SAMPLER_STEP", self._sampler_op(s, noise_ptr=None, noise_C=0, seed=0, sample0=0, hist_mode=mode, no_cfg=True))
+        corrector = o.score_corrector is not None
+        ev = lambda: self._eval_ops(s)
+        upd = lambda mode: self._update_op(s, hist_mode=mode, no_cfg=corrector)
         save = ("FRIDO_OP_COPY", dict(src=self.x.data_ptr(), dst=self.x_save.data_ptr(), n=nbytes))
         restore = ("FRIDO_OP_COPY", dict(src=self.x_save.data_ptr(), dst=self.x.data_ptr(), n=nbytes))
-        first_a = prog(save, upd(1), *([step_add(1)] if n > 1 else []))            # ... then the forward at (x_prev, t_next)
-        first_b = prog(*([step_add(-1)] if n > 1 else []), restore, upd(3), step_add(1))
-        body = prog(upd(1), step_add(1))
-        t_steps = self.t_loop.astype(np.int64)
-        p_drop = opts.get("noise_dropout", 0.0)
-        for i in range(n):
-            if draw is not None:          # eta == 0: the reference still draws (and discards) noise for every update
-                for _ in range(2 if i == 0 else 1):
-                    nz = draw((self.B, Cs, self.H, self.W))
-                    if p_drop > 0.:
-                        torch.nn.functional.dropout(nz, p=p_drop)
-            plan.step.run(sp)
-            self._corrected_eps(s, sp, Cs, t_steps[i], opts)
-            if i == 0:
-                first_a.run(sp)
-                plan.step.run(sp)
-                self._corrected_eps(s, sp, Cs, t_steps[min(i + 1, n - 1)], opts)      # t_next (plms.py:164-166)
-                first_b.run(sp)
-            else:
-                body.run(sp)
-            self._log(s, i, inter, log_every_t, sp, Cs, callback, img_callback)
+        ahead, back = ([1], [-1]) if n > 1 else ([], [])        # t_next for the second evaluation (plms.py:164-166)
+        log = lambda i: self._log(s, i, sp, o)
 
-    def _plms_stage(self, s, sp, draw, seed, sample0, inter, log_every_t, callback, img_callback, Cs):
-        """plms.py:156-194,285-303: Heun-style first step (two denoiser calls), then Adams-Bashforth 2/3/4.  Two captured
-        hipGraphs per stage serve every step: `first` = [forward, save x, update with e_t (eps -> ring slot 0), step+1,
-        forward at (x_prev, t_next), step-1, restore x, update with (e_t + e_next)/2, step+1]; `body` = [forward, update with
-        the ring history selected by the device step counter, step+1].  eta == 0 (plms.py:25-26), so no noise enters the
-        update and the same graphs serve the philox / torch / tape modes."""
-        from .engine import Prog
-        opts = getattr(self, "_opts", {})
-        if opts.get("score_corrector") is not None:
-            return self._plms_stage_with_corrector(s, sp, draw, seed, sample0, inter, log_every_t, callback, img_callback, Cs, opts)
-        plan = self.stages[s]
-        n = self.n_steps
-        self.rng.copy_(torch.tensor([seed, sample0], dtype=torch.int64))
-        nbytes = self.x.numel() * 4
-
-        def build(first):
-            p = self._prog()
-            p.ops = self._eval_ops(s)
-            if first:
-                p.emit("FRIDO_OP_COPY", src=self.x.data_ptr(), dst=self.x_save.data_ptr(), n=nbytes)
-                p.emit("FRIDO_OP_SAMPLER_STEP", **self._sampler_op(s, noise_ptr=None, noise_C=0, seed=0, sample0=0, hist_mode=1))
-                if n > 1:
-                    self._step_add(p, 1)
-                p.ops += self._eval_ops(s)
-                if n > 1:
-                    self._step_add(p, -1)
-                p.emit("FRIDO_OP_COPY", src=self.x_save.data_ptr(), dst=self.x.data_ptr(), n=nbytes)
-                p.emit("FRIDO_OP_SAMPLER_STEP", **self._sampler_op(s, noise_ptr=None, noise_C=0, seed=0, sample0=0, hist_mode=3))
-            else:
-                p.emit("FRIDO_OP_SAMPLER_STEP", **self._sampler_op(s, noise_ptr=None, noise_C=0, seed=0, sample0=0, hist_mode=1))
-            self._step_add(p, 1)
-            p.keep = [plan]
-            return p.capture(sp) if self.use_graph else p
-
-        for name, first in (("plms_first", True), ("plms_body", False)):
-            if (name, s) not in self.graphs:
-                self.graphs[(name, s)] = build(first)
-        g_first, g_body = self.graphs[("plms_first", s)], self.graphs[("plms_body", s)]
-        go = (lambda g: g.launch(sp)) if self.use_graph else (lambda g: g.run(sp))
-        for i in range(n):
+        def draws(i, unit):
             # eta == 0: the reference still draws (and discards) noise for every update; keep a replayed stream in step
-            if draw is not None:
-                p_drop = getattr(self, "_opts", {}).get("noise_dropout", 0.0)
+            if o.draw is not None:
                 for _ in range(2 if i == 0 else 1):
-                    nz = draw((self.B, Cs, self.H, self.W))
-                    if p_drop > 0.:
-                        torch.nn.functional.dropout(nz, p=p_drop)      # (plms.py get_x_prev_and_pred_x0: the mask draw consumes generator state)
-            go(g_first if i == 0 else g_body)
-            self._log(s, i, inter, log_every_t, sp, Cs, callback, img_callback)
-
+                    nz = o.draw((self.B, sum(self.embed[:s + 1]), self.H, self.W))
+                    if o.noise_dropout > 0.:
+                        torch.nn.functional.dropout(nz, p=o.noise_dropout)      # (plms.py get_x_prev_and_pred_x0: the mask draw consumes generator state)
+        if corrector:       # step 0 needs the hook twice, inside what is one body otherwise: a loop of its own
+            first_a, first_b, body = self._prog([save, upd(1)] + ahead), self._prog(back + [restore, upd(3), 1]), self._prog([upd(1), 1])
+            for i in range(n):
+                draws(i, 1)
+                plan.step.run(sp)
+                self._corrected_eps(s, sp, self.t_loop[i], o)
+                if i == 0:
+                    first_a.run(sp)
+                    plan.step.run(sp)
+                    self._corrected_eps(s, sp, self.t_loop[min(1, n - 1)], o)
+                    first_b.run(sp)
+                else:
+                    body.run(sp)
+                log(i)
+            return
+        first = self._body(("plms_first", s), sp, lambda: [ev(), save, upd(1)] + ahead + [ev()] + back + [restore, upd(3), 1])
+        self._body(("plms_body", s), sp, lambda: [ev(), upd(1), 1])
+        self._replay(("plms_body", s), 1, None, sp, before_unit=draws, after_unit=log, first=first)
 
     # ---- ancestral (DDPM) loop ---------------------------------------------------------------------------
     @torch.no_grad()
@@ -700,10 +638,10 @@ class SamplerEngine:
         product noise * temperature[t] is formed on the host, where the reference forms it).  Captured step bodies are replayed in units
         of up to GRAPH_STEPS steps; a step whose result is logged ends its unit; callbacks make every unit one step long; a score corrector
         runs forward program, hook and update kernel eagerly.  Returns (img NCHW, list of logged tensors)."""
-        B, C, H, W, n = self.B, self.C, self.H, self.W, self.n_steps
+        n = self.n_steps
         if noise_dropout > 0. and noise == "philox":
             raise NotImplementedError("noise_dropout draws its keep mask from torch's generator: use noise='torch' (or a recorded tape)")
-        draw = (lambda shape: torch.randn(shape)) if noise == "torch" else (noise if callable(noise) else None)
+        draw = self._host_draw(noise)
         if isinstance(temperature, (list, tuple)):
             if draw is None:
                 raise NotImplementedError("a per-timestep temperature list needs host noise (noise='torch' or a tape): the Philox form multiplies in the kernel by one scalar")
@@ -712,139 +650,61 @@ class SamplerEngine:
         else:
             temps = [float(temperature)] * n
             assert draw is not None or float(temperature) == self.temperature, "the Philox form bakes its temperature into the engine"
-        opts = dict(noise_dropout=float(noise_dropout), score_corrector=score_corrector, corrector_kwargs=dict(corrector_kwargs or {}),
-                    model=model, cond=cond, temps=temps)
-        stream = self._stream_ptr()
-        stream.wait_stream(torch.cuda.current_stream(self.dev))
-        sp = stream.cuda_stream
-        with torch.cuda.stream(stream):
-            ctx = cond.to(self.dev, torch.float32 if not self.labels or cond.is_floating_point() else torch.int64) if cond is not None else None
-            if x_T is not None:
-                xt = torch.as_tensor(x_T, dtype=torch.float32)
-            else:
-                xt = draw((B, C, H, W)) if draw is not None else None
-            if xt is not None:
-                xd = torch.as_tensor(xt, dtype=torch.float32).to(self.dev).contiguous()
-                assert xd.shape == (B, C, H, W), (tuple(xd.shape), (B, C, H, W))
-                _run1(self.b, "FRIDO_OP_RELAYOUT", sp, src=xd.data_ptr(), dst=self.x.data_ptr(), B=B, HW=H * W, Csrc=C, c0=0, Cuse=C, Cdst=C,
-                      d0=0, to_nchw=0)
-            else:
-                _run1(self.b, "FRIDO_OP_RANDN", sp, dst=self.x.data_ptr(), n=B * H * W * C, per_sample=H * W * C, seed=seed, sample0=sample0,
-                      rng_stream=0)
-            inter = [self._to_nchw(self.x, sp)] if collect == "img" else []
+        o = SimpleNamespace(draw=draw, seed=seed, sample0=sample0, log_every_t=log_every_t, callback=callback, img_callback=img_callback,
+                            noise_dropout=float(noise_dropout), score_corrector=score_corrector, corrector_kwargs=dict(corrector_kwargs or {}),
+                            model=model, cond=cond, temps=temps, collect=collect)
+        with self._own_stream() as sp:
+            ctx = self._context(cond)
+            self._init_x(x_T, draw, seed, sample0, sp)
+            o.inter = [self._to_nchw(self.x, sp)] if collect == "img" else []
             t_loop = torch.from_numpy(self.t_loop.astype(np.int64)).to(self.dev)
             self.rng.copy_(torch.tensor([seed, sample0], dtype=torch.int64))
             for s in range(self.num_stage):
-                plan = self.stages[s]
-                if self.labels:
-                    plan.set_labels(ctx)
-                elif ctx is not None:
-                    plan.set_context(ctx)
-                plan.set_timesteps(t_loop)
-                self.step.zero_()
-                if self.labels:
-                    self.step_bx.zero_()
-                plan.pre.run(sp)
-                self._ddpm_stage(s, sp, draw, inter, log_every_t, callback, img_callback, opts, collect)
+                self._bind_stage(s, ctx, t_loop, sp)
+                self._ddpm_stage(s, sp, o)
             out = self._to_nchw(self.x, sp)
-        torch.cuda.current_stream(self.dev).wait_stream(stream)
-        return out, inter
+        return out, o.inter
 
-    def _ancestral_op(self, s, tape):
-        B, HW, C = self.B, self.H * self.W, self.C
-        kw = dict(x=self.x.data_ptr(), B=B, HW=HW, Cx=C, start=sum(self.embed[:s]), nch=self.embed[s], eps_cond=self.stages[s].eps.data_ptr(),
-                  x_out=self.x.data_ptr(), pred_x0=self.pred_x0.data_ptr(), write_x=1, hist_mode=_lib.STEP_ANCESTRAL)
-        if tape:      # this unit's noise (already multiplied by its temperature) and coefficient rows, by the unit's own counter
-            kw.update(coef=self.coef_c.data_ptr(), step=self.step_c.data_ptr(), temperature=1.0, noise=self.tape.data_ptr(),
-                      noise_stride=B * HW * C, noise_C=C, noise_c0=0)
-        else:
-            kw.update(coef=self.coef.data_ptr(), coef_row_offset=self.row0, step=self.step.data_ptr(), temperature=self.temperature,
-                      rng_stream=s + 1, rng_dev=self.rng.data_ptr())
-        return kw
-
-    def _ddpm_stage(self, s, sp, draw, inter, log_every_t, callback, img_callback, opts, collect):
-        from .engine import Prog
-        plan = self.stages[s]
-        n, B, C, H, W = self.n_steps, self.B, self.C, self.H, self.W
-        tape = draw is not None
+    def _ddpm_stage(self, s, sp, o):
+        plan, n = self.stages[s], self.n_steps
+        B, C, H, W = self.B, self.C, self.H, self.W
+        tape = o.draw is not None
         if tape and self.tape is None:
             self.tape = torch.empty(self.unit, B, H, W, C, dtype=torch.float32, device=self.dev)
-        corrector = opts["score_corrector"] is not None
+        noise = (self.tape.data_ptr(), C) if tape else None
+        update = lambda: [self._update_op(s, noise), 1] + ([("FRIDO_OP_STEP_ADD", dict(step=self.step_c.data_ptr(), delta=1))] if tape else [])
+        logged = logged_at(n, o.log_every_t)          # frido.py:1409: i % log_every_t == 0 or i == timesteps - 1, i = t
 
-        def update_ops(p):
-            p.emit("FRIDO_OP_SAMPLER_STEP", **self._ancestral_op(s, tape))
-            self._step_add(p, 1)
-            if tape:
-                p.emit("FRIDO_OP_STEP_ADD", step=self.step_c.data_ptr(), delta=1)
-        key = ("ddpm_tape" if tape else "ddpm", s)
-        if corrector:
-            upd = Prog(self.dev, self.b.nsplit)
-            update_ops(upd)
-        elif key not in self.graphs:
-            body = Prog(self.dev, self.b.nsplit)
-            body.ops = list(plan.step.ops)
-            update_ops(body)
-            body.keep = [plan]
-            self.graphs[key] = body.capture(sp) if self.use_graph else body
-            self.graph_captures = getattr(self, "graph_captures", 0) + 1
-        K = self.unit if (self.use_graph and not corrector and callback is None and img_callback is None) else 1
-        gk = None
-        if K > 1 and n >= K:
-            kkey = key + ("x%d" % K,)
-            if kkey not in self.graphs:
-                multi = Prog(self.dev, self.b.nsplit)
-                multi.ops = list(self.graphs[key].keep[1].ops) * K
-                multi.keep = [plan]
-                self.graphs[kkey] = multi.capture(sp)
-                self.graph_captures = getattr(self, "graph_captures", 0) + 1
-            gk = self.graphs[kkey]
-        logged = lambda i: (n - 1 - i) % log_every_t == 0 or i == 0          # frido.py:1409: i % log_every_t == 0 or i == timesteps - 1, i = t
-        p_drop = opts["noise_dropout"]
-        i = 0
-        while i < n:
-            unit = K if (gk is not None and i + K <= n and not any(logged(j) for j in range(i, i + K - 1))) else 1
+        def upload(i, unit):
             if tape:
                 rows = []
                 for j in range(i, i + unit):
-                    nz = torch.as_tensor(draw((B, C, H, W)), dtype=torch.float32) * opts["temps"][n - 1 - j]      # frido.py:1286
-                    rows.append(torch.nn.functional.dropout(nz, p=p_drop) if p_drop > 0. else nz)                 # frido.py:1288-1289
-                self.tape[:unit].copy_(torch.stack(rows).permute(0, 1, 3, 4, 2))                                  # plumbing: layout + H2D
+                    nz = torch.as_tensor(o.draw((B, C, H, W)), dtype=torch.float32) * o.temps[n - 1 - j]                      # frido.py:1286
+                    rows.append(torch.nn.functional.dropout(nz, p=o.noise_dropout) if o.noise_dropout > 0. else nz)         # frido.py:1288-1289
+                self.tape[:unit].copy_(torch.stack(rows).permute(0, 1, 3, 4, 2))                                           # plumbing: layout + H2D
                 self.coef_c[:unit].copy_(self.coef[self.row0 + i:self.row0 + i + unit])
                 self.step_c.zero_()
-            if corrector:
-                plan.step.run(sp)
-                self._corrected_eps_full(s, sp, int(self.t_loop[i]), opts)
-                upd.run(sp)
-            elif unit > 1:
-                gk.launch(sp)
-                self.multi_step_launches = getattr(self, "multi_step_launches", 0) + 1
-            elif self.use_graph:
-                self.graphs[key].launch(sp)
-            else:
-                self.graphs[key].run(sp)
-            i += unit
-            t = n - i
-            if logged(i - 1):
-                inter.append(self._to_nchw(self.x if collect == "img" else self.pred_x0, sp))
-            if callback:
-                callback(t)
-            if img_callback:
-                img_callback(self._to_nchw(self.x, sp), t)
 
-    def _corrected_eps_full(self, s, sp, t_value, opts):
-        """frido.py:1233-1241: the split head's eps zero-padded to the latent's channels, `score_corrector.modify_score(model, model_out, x, t,
-        c, **kwargs)` on torch tensors (NCHW), the stage's channels written back as the eps the update kernel reads."""
-        plan = self.stages[s]
-        B, C, H, W = self.B, self.C, self.H, self.W
-        start, nch = sum(self.embed[:s]), self.embed[s]
-        e = plan.eps.view(B, H, W, nch).permute(0, 3, 1, 2)
-        e_t = torch.cat((torch.zeros(B, start, H, W, device=self.dev), e, torch.zeros(B, C - start - nch, H, W, device=self.dev)), dim=1)
-        t = torch.full((B,), int(t_value), device=self.dev, dtype=torch.long)
-        e_new = opts["score_corrector"].modify_score(opts["model"], e_t, self._to_nchw(self.x, sp), t, opts["cond"], **opts["corrector_kwargs"])
-        e_new = e_new.to(torch.float32).contiguous()
-        assert e_new.shape == (B, C, H, W), "modify_score must return a tensor of model_out's shape"
-        _run1(self.b, "FRIDO_OP_RELAYOUT", sp, src=e_new.data_ptr(), dst=plan.eps.data_ptr(), B=B, HW=H * W, Csrc=C, c0=start, Cuse=nch,
-              Cdst=nch, d0=0, to_nchw=0)
+        def after(i):
+            t = n - 1 - i
+            if logged(i):
+                o.inter.append(self._to_nchw(self.x if o.collect == "img" else self.pred_x0, sp))
+            if o.callback:
+                o.callback(t)
+            if o.img_callback:
+                o.img_callback(self._to_nchw(self.x, sp), t)
+        if o.score_corrector is not None:
+            upd = self._prog(update())
+            for i in range(n):
+                upload(i, 1)
+                plan.step.run(sp)
+                self._corrected_eps(s, sp, self.t_loop[i], o)
+                upd.run(sp)
+                after(i)
+            return
+        key = ("ddpm_tape" if tape else "ddpm", s)
+        self._body(key, sp, lambda: [self._eval_ops(s)] + update())
+        self._replay(key, self._unit_steps(o, self.unit), logged, sp, before_unit=upload, after_unit=after)
 
 
 class DecoderRuntime:
@@ -882,15 +742,13 @@ class DecoderRuntime:
             for dst, src in zip(plan.force_idx, force_codes):
                 dst.copy_(torch.as_tensor(src, dtype=torch.int64).reshape(-1))
         zc = z.contiguous().float()
-        _run1(self.b, "FRIDO_OP_RELAYOUT", st, src=zc.data_ptr(), dst=z_state.data_ptr(), B=B, HW=h * w, Csrc=Ct, c0=0,
-              Cuse=Ct, Cdst=Ct, d0=0, to_nchw=0)
+        _relayout(self.b, st, zc, z_state, B, h * w, Ct, 0)
         plan.prog.run(st)
         if u8:
             img = plan.out_u8.view(B, plan.H, plan.W, plan.a.out_ch).clone()
             return (img, [i.view(B, -1) for i in plan.idx]) if return_code else img
         out = torch.empty(B, plan.a.out_ch, plan.H, plan.W, dtype=torch.float32, device=self.device)
-        _run1(self.b, "FRIDO_OP_RELAYOUT", st, src=plan.out_nhwc.data_ptr(), dst=out.data_ptr(), B=B, HW=plan.H * plan.W,
-              Csrc=plan.a.out_ch, c0=0, Cuse=plan.a.out_ch, Cdst=plan.a.out_ch, d0=0, to_nchw=1)
+        _relayout(self.b, st, plan.out_nhwc, out, B, plan.H * plan.W, plan.a.out_ch, 1)
         if return_code:
             return out, [i.view(B, -1) for i in plan.idx]
         return out

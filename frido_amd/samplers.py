@@ -80,21 +80,43 @@ class _SamplerBase:
         self.ddim_sqrt_one_minus_alphas = np.sqrt((np.float32(1.0) - al).astype(np.float32))
         self.alphas_cumprod = ac
 
-    def _engine(self, B, shape, nctx, S, eta, scale, num_stage, temperature, replica=0, patch=None):
+    def _engine(self, B, shape, nctx, S, eta, scale, num_stage, temperature, replica=0, patch=None, solver=None):
+        """The cached SamplerEngine of this call.  solver: DPM-Solver++'s (order, skip_type, lower_order_final), part of its engine's key where
+        DDIM / PLMS have eta and the temperature; its table is computed from the float64 schedule."""
         from .runtime import SamplerEngine
         unet = self.model.model.diffusion_model
         rt = unet.runtime()
         C, H, W = shape
-        key = (self.KIND, B, C, H, W, nctx, S, float(eta), scale != 1.0, num_stage, float(temperature), replica)
+        if solver is None:
+            key = (self.KIND, B, C, H, W, nctx, S, float(eta), scale != 1.0, num_stage, float(temperature), replica)
+            more, ac = dict(temperature=temperature, patch=patch), self.model.alphas_cumprod.detach().float()
+        else:
+            key = (self.KIND, B, C, H, W, nctx, S, scale != 1.0, num_stage, replica) + solver
+            more, ac = dict(zip(("order", "skip_type", "lower_order_final"), solver)), self.model.alphas_cumprod.detach().double()
         if patch is not None:      # patch-wise mode (model.split_input_params): plans, buffers and graphs of its own
             from .patching import geometry_key
             key += (geometry_key(patch),)
         eng = cached_engine(rt, key, lambda: SamplerEngine(
             rt.builder_for(replica), unet.cfg, B=B, C=C, H=H, W=W, nctx=nctx if isinstance(nctx, int) else 0, S=S, eta=eta, kind=self.KIND,
-            alphas_cumprod=self.model.alphas_cumprod.detach().float().cpu().numpy(), embed_dim=self.model.embed_dim_list, cfg_scale=scale,
-            num_stage=num_stage, temperature=temperature, patch=patch))
+            alphas_cumprod=ac.cpu().numpy(), embed_dim=self.model.embed_dim_list, cfg_scale=scale, num_stage=num_stage, **more))
         eng.cfg_scale = float(scale)      # read from a device scalar by the captured step bodies: one graph, any scale
         return eng
+
+    def _check_guidance(self, conditioning, unconditional_conditioning, scale, batch_size):
+        """What every `sample` asks of its conditioning pair; returns the engine-cache mode: the context length, or which conditioning mode
+        the plans were built for (check_conditioning)."""
+        unet = getattr(getattr(self.model, "model", None), "diffusion_model", None)
+        mode = check_conditioning(unet, conditioning, batch_size)
+        if conditioning is None:
+            if scale != 1.:
+                raise ValueError("classifier-free guidance needs a conditioning")
+        else:
+            if unconditional_conditioning is not None and unconditional_conditioning.shape != conditioning.shape:
+                raise ValueError(f"unconditional_conditioning {tuple(unconditional_conditioning.shape)} must match "
+                                 f"conditioning {tuple(conditioning.shape)}")
+            if not conditioning.is_cuda:
+                raise FridoHipError("sample(): conditioning must live on the MI355X (there is no CPU path)")
+        return mode
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, num_stage=1, callback=None, normals_sequence=None,
@@ -110,7 +132,6 @@ class _SamplerBase:
                                       "x0 and the per-stage latent, ddim.py:158-161); not provided on the HIP path")
         if quantize_x0:
             raise NotImplementedError("quantize_x0: the reference calls exit() on this option (ddim.py:251-253)")
-        unet = getattr(getattr(self.model, "model", None), "diffusion_model", None)
         # patch-wise mode (frido.py:1076-1152): the samplers inherit it from apply_model; looked up on every call, like the reference's hasattr
         from . import patching
         patch = patching.params_of(self.model)
@@ -120,17 +141,7 @@ class _SamplerBase:
             patching.check_conditioning(self.model, conditioning)
             patching.check_conditioning(self.model, unconditional_conditioning)
             patching.geometry(patch, shape[1], shape[2], patching.MODEL, None)      # the geometry's own refusals, before anything is planned
-        # engine-cache key: context length, or which conditioning mode the plans were built for
-        mode = check_conditioning(unet, conditioning, batch_size)
-        if conditioning is None:
-            if unconditional_guidance_scale != 1.:
-                raise ValueError("classifier-free guidance needs a conditioning")
-        else:
-            if unconditional_conditioning is not None and unconditional_conditioning.shape != conditioning.shape:
-                raise ValueError(f"unconditional_conditioning {tuple(unconditional_conditioning.shape)} must match "
-                                 f"conditioning {tuple(conditioning.shape)}")
-            if not conditioning.is_cuda:
-                raise FridoHipError("sample(): conditioning must live on the MI355X (there is no CPU path)")
+        mode = self._check_guidance(conditioning, unconditional_conditioning, unconditional_guidance_scale, batch_size)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         if unconditional_guidance_scale != 1.:
             assert unconditional_conditioning is not None
@@ -196,17 +207,7 @@ class DPMSolverSampler(_SamplerBase):
             raise ValueError(f"DPMSolverSampler: unknown skip_type {skip_type!r}, one of {schedules.DPM_SKIP_TYPES}")
         ac = self.model.alphas_cumprod.detach().double().cpu().numpy()
         self.timesteps, _ = schedules.dpm_solver_table(ac, S, skip_type, order, lower_order_final)      # a grid with no step: ValueError
-        unet = getattr(getattr(self.model, "model", None), "diffusion_model", None)
-        mode = check_conditioning(unet, conditioning, batch_size)
-        if conditioning is None:
-            if unconditional_guidance_scale != 1.:
-                raise ValueError("classifier-free guidance needs a conditioning")
-        else:
-            if unconditional_conditioning is not None and unconditional_conditioning.shape != conditioning.shape:
-                raise ValueError(f"unconditional_conditioning {tuple(unconditional_conditioning.shape)} must match "
-                                 f"conditioning {tuple(conditioning.shape)}")
-            if not conditioning.is_cuda:
-                raise FridoHipError("sample(): conditioning must live on the MI355X (there is no CPU path)")
+        mode = self._check_guidance(conditioning, unconditional_conditioning, unconditional_guidance_scale, batch_size)
         if unconditional_guidance_scale != 1.:
             assert unconditional_conditioning is not None
         if verbose:
@@ -215,22 +216,8 @@ class DPMSolverSampler(_SamplerBase):
         solver = (int(order), skip_type, bool(lower_order_final))
 
         def go(noise_src):
-            eng = self._dpm_engine(batch_size, tuple(shape), mode, S, unconditional_guidance_scale, num_stage, replica, solver)
+            eng = self._engine(batch_size, tuple(shape), mode, S, 0.0, unconditional_guidance_scale, num_stage, 1.0, replica, solver=solver)
             return eng.run(conditioning, unconditional_conditioning, x_T=x_T, noise=noise_src, seed=seed, sample0=sample0,
                            log_every_t=log_every_t, callback=callback, img_callback=img_callback, model=self.model)
         from . import autoplanes
         return autoplanes.run(self.model.model.diffusion_model, go, f"{type(self).__name__}.sample", noise=noise)
-
-    def _dpm_engine(self, B, shape, nctx, S, scale, num_stage, replica, solver):
-        from .runtime import SamplerEngine
-        unet = self.model.model.diffusion_model
-        rt = unet.runtime()
-        C, H, W = shape
-        key = (self.KIND, B, C, H, W, nctx, S, scale != 1.0, num_stage, replica) + solver
-        order, skip_type, lower_order_final = solver
-        eng = cached_engine(rt, key, lambda: SamplerEngine(
-            rt.builder_for(replica), unet.cfg, B=B, C=C, H=H, W=W, nctx=nctx if isinstance(nctx, int) else 0, S=S, eta=0.0, kind=self.KIND,
-            alphas_cumprod=self.model.alphas_cumprod.detach().double().cpu().numpy(), embed_dim=self.model.embed_dim_list, cfg_scale=scale,
-            num_stage=num_stage, order=order, skip_type=skip_type, lower_order_final=lower_order_final))
-        eng.cfg_scale = float(scale)      # read from a device scalar by the captured step bodies: one graph, any scale
-        return eng

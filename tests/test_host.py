@@ -449,3 +449,25 @@ def test_auto_plane_selection_host_logic(monkeypatch):
             warnings.simplefilter("error")
             assert autoplanes.run(mod, lambda n: "x", "t") == "x"
         assert len(polled) == n0 and mod.invalidated == 0
+
+
+@pytest.mark.parametrize("n,K,log,want", [(10, 4, 5, [1, 4, 4, 1]), (6, 2, 100, [1, 2, 2, 1]), (5, 20, 2, [1] * 5), (10, 1, 5, [1] * 10),
+                                          (7, 1, 1, [1] * 7), (9, 3, 4, None), (23, 5, 7, None), (8, 8, 100, None), (12, 4, 1, None)])
+def test_replay_units_cover_every_step_and_end_where_the_host_is_needed(n, K, log, want):
+    """The unit schedule of SamplerEngine._replay: a K-step unit only where a K-step graph exists (K > 1, n >= K), fits and holds no step
+    that needs the host before its last; everything else single steps."""
+    from frido_amd.runtime import logged_at, replay_units
+    host_at = logged_at(n, log)
+    assert [i for i in range(n) if host_at(i)] == [i for i in range(n) if (n - 1 - i) % log == 0 or i == 0]
+    units = replay_units(n, K, host_at)
+    if want is not None:
+        assert units == want
+    assert sum(units) == n and set(units) <= {1, K}
+    if K == 1 or n < K:
+        assert units == [1] * n
+    i = 0
+    for u in units:
+        assert not any(host_at(j) for j in range(i, i + u - 1))      # a step the host must see is the last of its unit
+        # greedy: a single step is taken only where a K-unit is not possible
+        assert u == K or K == 1 or n < K or i + K > n or any(host_at(j) for j in range(i, i + K - 1))
+        i += u

@@ -70,10 +70,7 @@ def main():
     engines = unet.runtime()._sampler_engines
     for key, eng in engines.items():
         s = 1
-        if eng.kind == "ddpm":
-            kw, label = eng._ancestral_op(s, tape=False), "ancestral_step_kernel"
-        else:
-            kw, label = eng._sampler_op(s, noise_ptr=None, noise_C=0, seed=0, sample0=0), "sampler_step_kernel (ddim, eta 1)"
+        kw, label = eng._update_op(s)[1], "ancestral_step_kernel" if eng.kind == "ddpm" else "sampler_step_kernel (ddim, eta 1)"
         n = 200
         p = Prog(dev, 2)
         for _ in range(n):

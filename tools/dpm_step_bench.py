@@ -81,7 +81,7 @@ def main():
     for name, eng in engines.items():
         HW, Cn, nch = eng.H * eng.W, eng.C, eng.embed[s]
         if name == "dpm_2m":
-            desc = eng._dpm_desc(s)
+            desc = eng._update_op(s)[1]
             desc.x_out = scratch.data_ptr()
             L = _lib.lib(eng.planes)
             run = lambda: [_lib.check(L.frido_dpm_step(C.byref(desc), st.cuda_stream), "frido_dpm_step") for _ in range(n)]
@@ -91,7 +91,7 @@ def main():
         else:
             p = Prog(dev, 2)
             for _ in range(n):
-                p.emit("FRIDO_OP_SAMPLER_STEP", **eng._sampler_op(s, noise_ptr=None, noise_C=0, seed=0, sample0=0, x_out=scratch.data_ptr()))
+                p.emit("FRIDO_OP_SAMPLER_STEP", **dict(eng._update_op(s)[1], x_out=scratch.data_ptr()))
             run = lambda p=p: p.run(st.cuda_stream)
             nbytes, label = B * HW * ((s + 1) * nch + nch + 2 * (s + 1) * nch) * 4, "sampler_step_kernel (ddim, eta 0)"
             eng.step.zero_()
