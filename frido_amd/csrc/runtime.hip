@@ -326,6 +326,7 @@ extern "C" int frido_sizeof_desc(int32_t kind) {
         case FRIDO_OP_SYNC: return sizeof(FridoSync);
         case FRIDO_OP_L2NORM: return sizeof(FridoL2Norm);
         case FRIDO_OP_ATTN_MH: return sizeof(FridoAttnMh);
+        case FRIDO_DESC_KEEP_BLEND: return sizeof(FridoKeepBlend);
         default: return -1;
     }
 }
@@ -408,7 +409,7 @@ extern "C" int frido_status_poll(frido_stream_t stream, uint32_t* flags, int32_t
     return FRIDO_OK;
 }
 
-// diagnostic: the word of ONE translation unit (registration = link order: igemm, convgn, norm, misc, attn, flash, flash_mh, runtime, dpmstep); -1 past the end
+// diagnostic: the word of ONE translation unit (registration = link order: igemm, convgn, norm, misc, attn, flash, flash_mh, runtime, dpmstep, edit); -1 past the end
 extern "C" int frido_status_word_of(int32_t idx, uint32_t* word) {
     if (idx < 0 || idx >= (int)status_words().size() || !word) return -1;
     unsigned w = 0;

@@ -93,3 +93,36 @@ def sample_images(model, cond, *, S, eta=1.0, sampler="ddim", scale=1.0, uncond=
         from . import _lib
         _lib.warn_on_status("sample_images")
     return all_gather_images(img, total=total) if gather else img
+
+
+@torch.no_grad()
+def edit_images(model, images, cond, *, S, strength, keep_mask=None, eta=1.0, scale=1.0, uncond=None, seed=0, sample0=0, noise="philox",
+                num_stage=None, init="z0", reimpose=True, gather=True, total=None, log_every_t=10 ** 9, gather_dtype="float32",
+                check_status=True):
+    """Image-to-image / inpainting on this rank's shard: images (b, 3, H, W) in [-1, 1] on the GPU -> encode_first_stage +
+    get_first_stage_encoding -> DDIMSampler.edit (the last clamp(int(strength * S), 1, S) of S steps per stage) -> decode_first_stage.
+    keep_mask (b, 1, H, W) in [0, 1] over the PIXELS, 1 = keep: min-pooled to the latent grid (a latent cell is kept only if every pixel
+    it decodes to is).  Noise is keyed by (seed, GLOBAL sample index = sample0 + i), so a sharded run equals the whole batch; gather /
+    gather_dtype / check_status as in sample_images."""
+    from .samplers import DDIMSampler
+    unet = model.model.diffusion_model
+    z0 = model.get_first_stage_encoding(model.encode_first_stage(images))
+    m = None
+    if keep_mask is not None:
+        if keep_mask.dim() != 4 or keep_mask.shape[:2] != (images.shape[0], 1) or keep_mask.shape[2:] != images.shape[2:]:
+            raise ValueError(f"edit_images: keep_mask must be {(images.shape[0], 1) + tuple(images.shape[2:])}, got {tuple(keep_mask.shape)}")
+        f = images.shape[2] // z0.shape[2]
+        m = -torch.nn.functional.max_pool2d(-keep_mask.float(), f, f) if f > 1 else keep_mask.float()
+    z, _ = DDIMSampler(model).edit(S, z0, cond, strength=strength, keep_mask=m, init=init, reimpose=reimpose, num_stage=num_stage or unet.num_stage,
+                                   eta=eta, unconditional_guidance_scale=scale, unconditional_conditioning=uncond, noise=noise, seed=seed,
+                                   sample0=sample0, log_every_t=log_every_t, verbose=False)
+    if gather_dtype == "float32":
+        img = model.decode_first_stage(z)
+    elif gather_dtype in ("uint8", "uint8_pil"):
+        img = model.decode_first_stage(z, to_uint8="pil" if gather_dtype == "uint8_pil" else "np")
+    else:
+        raise ValueError(f"gather_dtype {gather_dtype!r}: 'float32', 'uint8' or 'uint8_pil'")
+    if check_status and img.is_cuda:
+        from . import _lib
+        _lib.warn_on_status("edit_images")
+    return all_gather_images(img, total=total) if gather else img

@@ -31,6 +31,9 @@ from .vqgan_plan import VQDecodePlan, VQDecodeQuantPlan, VQEncodePlan
 GRAPH_STEPS = max(1, int(os.environ.get("FRIDO_GRAPH_STEPS", "20")))
 DPM_STEP = "dpm_step"
 FOREIGN[DPM_STEP] = "frido_dpm_step"      # op tag of the DPM-Solver++ update inside a step body (patching.PatchProg)
+KEEP_BLEND = "keep_blend"
+FOREIGN[KEEP_BLEND] = "frido_keep_blend"  # op tag of the editing blend (csrc/edit.hip) in front of a model evaluation
+EDIT_RNG_STREAM = 64                      # Philox stream of stage s's blend draws: 64 + s, apart from 0 (x_T) and 1 .. num_stage (the updates)
 
 
 def _weights_of(module, device):
@@ -187,16 +190,48 @@ def logged_at(n, log_every_t):
     return lambda i: (n - 1 - i) % log_every_t == 0 or i == 0
 
 
-def replay_units(n, K, host_at):
-    """The lengths of the units n steps are replayed in.  A K-step graph exists where K > 1 and n >= K; step i starts a K-unit where one
-    exists, i + K <= n and none of the steps i ... i + K - 2 needs the host (host_at(j): its result is logged) -- a step that does may only
-    END a unit.  Every other unit is one step."""
-    units, i = [], 0
+def replay_units(n, K, host_at, i0=0):
+    """The lengths of the units the steps i0 ... n - 1 of n are replayed in.  A K-step graph exists where K > 1 and n - i0 >= K; step i
+    starts a K-unit where one exists, i + K <= n and none of the steps i ... i + K - 2 needs the host (host_at(j): its result is logged) -- a
+    step that does may only END a unit.  Every other unit is one step."""
+    units, i = [], i0
     while i < n:
-        fits = K > 1 and n >= K and i + K <= n and not any(host_at(j) for j in range(i, i + K - 1))
+        fits = K > 1 and n - i0 >= K and i + K <= n and not any(host_at(j) for j in range(i, i + K - 1))
         units.append(K if fits else 1)
         i += units[-1]
     return units
+
+
+def stage_masks(mask, num_stage):
+    """A keep mask (B, 1, H, W) in [0, 1] (1 = keep) -> one mask per stage: stage s works on a grid 2^(num_stage - 1 - s) times coarser
+    (its result is block-averaged by the hand-off), so it uses the mask's MIN over those blocks, expanded back by nearest -- a coarse cell
+    is kept only if all of it is kept, and the hand-off's block mean never mixes kept and regenerated values.  Torch on the tiny mask,
+    once per call."""
+    out = []
+    for s in range(num_stage):
+        f = 2 ** (num_stage - 1 - s)
+        if f == 1:
+            out.append(mask)
+            continue
+        if mask.shape[2] % f or mask.shape[3] % f:
+            raise ValueError(f"a {mask.shape[2]} x {mask.shape[3]} mask does not split into the {f} x {f} blocks of stage {s}")
+        m = -torch.nn.functional.max_pool2d(-mask, f, f)
+        out.append(torch.nn.functional.interpolate(m, scale_factor=f, mode="nearest"))
+    return out
+
+
+class EditSpec:
+    """What SamplerEngine.run(edit=) needs to edit a latent instead of sampling one.
+    z0 (B, C, H, W): the clean latent, on the device.  k: steps per stage, the LAST k rows of the S-row chain.  sqrt_ac / sqrt_1mac: the
+    model's own sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod buffers (q_sample's coefficients).  masks: None or one (B, 1, H, W)
+    device mask per stage (stage_masks).  init: "z0" -- every stage starts from q_sample of z0's stage channels at the chain's first
+    timestep -- or "noise" (x_T or a draw).  blend: the window of every blend, "stage" = the stage's own channels [a_s, e_s), "reference"
+    = [0, e_s).  reimpose: a last noise-free blend after the stage's steps.  first_stage: stages below it keep the start state's channels."""
+
+    def __init__(self, z0, k, sqrt_ac, sqrt_1mac, masks=None, init="z0", blend="stage", reimpose=True, first_stage=0):
+        assert init in ("z0", "noise") and blend in ("stage", "reference"), (init, blend)
+        self.z0, self.k, self.sqrt_ac, self.sqrt_1mac, self.masks = z0, int(k), sqrt_ac, sqrt_1mac, masks
+        self.init, self.blend, self.reimpose, self.first_stage = init, blend, bool(reimpose), int(first_stage)
 
 
 class SamplerEngine:
@@ -311,7 +346,8 @@ class SamplerEngine:
         """A program for a step body -- in patch mode one whose op list may hold the unfold / fold launches, for the DPM solver one that may
         hold its update (an exported launcher too, not an op kind) -- filled from `ops`: a (tag, descriptor) pair is one op, a list holds
         finished ops (a model evaluation: _eval_ops), an int advances the step counter."""
-        p = PatchProg(self.dev, self.b.nsplit) if self.geo is not None or self.kind == "dpm" else Prog(self.dev, self.b.nsplit)
+        foreign = any(not isinstance(o, int) and o[0] in FOREIGN for op in ops for o in (op if isinstance(op, list) else [op]))
+        p = PatchProg(self.dev, self.b.nsplit) if self.geo is not None or foreign else Prog(self.dev, self.b.nsplit)
         for op in ops:
             if isinstance(op, int):
                 self._step_add(p, op)
@@ -377,17 +413,18 @@ class SamplerEngine:
     def _go(self, g, sp):
         g.launch(sp) if self.use_graph else g.run(sp)
 
-    def _replay(self, key, K, host_at, sp, before_unit=None, after_unit=None, first=None):
+    def _replay(self, key, K, host_at, sp, before_unit=None, after_unit=None, first=None, n=None, i0=0):
         """All n steps of a stage from the body under `key`, in the units of replay_units.  K > 1: the same body K times in ONE captured graph
         (the device step counter makes every repetition pick its own timestep / noise slice), replayed wherever the K - 1 steps in between need
         no host access: fewer graph launches -- the trace shows ~30 us between the last kernel of one replay and the first of the next
         (profiles/r05_x3_gap_analysis.json).  before_unit(i, length) / after_unit(last step) are the kind's host work around a unit; `first`:
-        the body of step 0 where it differs (PLMS)."""
-        n, g = self.n_steps, self.graphs[key]
+        the body of step 0 where it differs (PLMS).  n / i0 (an edit): the steps i0 ... n - 1 of a chain of n <= n_steps; the device counter
+        is where the chain left it, so the same bodies serve every start row."""
+        n, g = self.n_steps if n is None else n, self.graphs[key]
         # (Graph.keep = (packed descriptor array, the program it was captured from))
-        gk = self._body(key + ("x%d" % K,), sp, lambda: [list(g.keep[1].ops) * K]) if K > 1 and n >= K else None
-        i = 0
-        for unit in replay_units(n, K, host_at):
+        gk = self._body(key + ("x%d" % K,), sp, lambda: [list(g.keep[1].ops) * K]) if K > 1 and n - i0 >= K else None
+        i = i0
+        for unit in replay_units(n, K, host_at, i0):
             if before_unit is not None:
                 before_unit(i, unit)
             if unit > 1:
@@ -429,17 +466,18 @@ class SamplerEngine:
         """A per-sample input of the model ([xrep * B, ...]) repeated for its L crops (crop l of sample b is entry b * L + l)."""
         return t.repeat_interleave(self.geo.L, dim=0) if self.geo is not None and t is not None else t
 
-    def _bind_stage(self, s, ctx, t_loop, sp):
-        """Stage s's plan on this run's conditioning and timesteps, the step counters at 0, the per-sample invariants (`pre`) computed."""
+    def _bind_stage(self, s, ctx, t_loop, sp, row0=0):
+        """Stage s's plan on this run's conditioning and timesteps, the step counters at row0 (0: the whole chain; an edit of k steps starts
+        at row n_steps - k, and the time-embedding rows follow the same counter), the per-sample invariants (`pre`) computed."""
         plan = self.stages[s]
         if self.labels:
             plan.set_labels(self._per_crop(ctx))
         elif ctx is not None:
             plan.set_context(self._per_crop(ctx))
         plan.set_timesteps(t_loop)
-        self.step.zero_()
+        self.step.fill_(row0)
         if self.labels:
-            self.step_bx.zero_()
+            self.step_bx.fill_(row0 * self.Bm * self.xrep)
         if self.geo is not None:
             from .patching import launch_unfold
             launch_unfold(self.unfold_x, sp)
@@ -460,16 +498,18 @@ class SamplerEngine:
         _relayout(self.b, sp, nhwc, out, self.B, self.H * self.W, nhwc.shape[-1], 1)
         return out
 
-    def _upload_noise(self, s, tape):
+    def _upload_noise(self, s, tape, row0=0, key=None):
         """tape: list of per-step NCHW tensors (B, 3(s+1), H, W) in draw order -> (address, channels) of the stage's persistent NHWC device
-        buffer (fixed address: the captured step body of the tape mode reads it by step index)."""
+        buffer of n_steps rows (fixed address: the captured step body of the tape mode reads it by step index).  row0: the row of the
+        tape's first entry (an edit's chain starts there); key: a buffer of its own beside the update's (the blend draws of an edit)."""
         Cs = sum(self.embed[:s + 1])
+        key = s if key is None else key
         t = torch.stack([torch.as_tensor(n, dtype=torch.float32) for n in tape])     # [n][B][Cs][H][W]
-        assert t.shape[1:] == (self.B, Cs, self.H, self.W), (t.shape, Cs)
-        if s not in self._tape_bufs:
-            self._tape_bufs[s] = torch.empty(t.shape[0], self.B, self.H, self.W, Cs, dtype=torch.float32, device=self.dev)
-        self._tape_bufs[s].copy_(t.permute(0, 1, 3, 4, 2), non_blocking=False)      # plumbing: layout + H2D
-        return self._tape_bufs[s].data_ptr(), Cs
+        assert t.shape[1:] == (self.B, Cs, self.H, self.W) and row0 + t.shape[0] <= self.n_steps, (t.shape, Cs, row0)
+        if key not in self._tape_bufs:
+            self._tape_bufs[key] = torch.zeros(self.n_steps, self.B, self.H, self.W, Cs, dtype=torch.float32, device=self.dev)
+        self._tape_bufs[key][row0:row0 + t.shape[0]].copy_(t.permute(0, 1, 3, 4, 2), non_blocking=False)      # plumbing: layout + H2D
+        return self._tape_bufs[key].data_ptr(), Cs
 
     def _corrected_eps(self, s, sp, t_value, o):
         """`score_corrector.modify_score(model, e_t, x, t, c, **kwargs)` (ddim.py:228-230, plms.py:236-238, frido.py:1233-1241) on the eps the
@@ -494,7 +534,7 @@ class SamplerEngine:
     @torch.no_grad()
     @_lib.with_planes
     def run(self, cond, uncond=None, *, x_T=None, noise="philox", seed=0, sample0=0, log_every_t=100, callback=None,
-            img_callback=None, noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, model=None):
+            img_callback=None, noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, model=None, edit=None):
         """Runs all stages.  noise: "philox" (device counter RNG), "torch" (draw from torch's global CPU generator in
         exactly the reference's order -- the stream of a reference run on CPU with the same torch.manual_seed), or a
         callable shape -> tensor replaying a recorded tape.  A supplied x_T is, like in the reference (ddim.py:150-152,
@@ -504,8 +544,15 @@ class SamplerEngine:
         torch's generator right after the randn, so it exists in the host-noise modes only ("torch" / a tape).
         score_corrector (ddim.py:228-230): an arbitrary Python hook between the denoiser and the update -- a stage then runs
         step by step on the stream (forward program, hook on torch tensors, update kernel) instead of replaying a captured graph.
+        edit (an EditSpec; kind "ddim", whole-latent engines): img2img / keep-mask inpainting, see _edit_stage.  Every stage from
+        edit.first_stage on runs the LAST edit.k steps of the chain; the stages below it keep the start state's channels (no steps, no
+        hand-off: what an adopted x_T gets), and x_T is only the start state of init="noise", it adopts nothing by itself.
         Returns (samples NCHW, intermediates dict)."""
         assert self.kind != "ddpm", "an ancestral engine runs through run_ancestral()"
+        if edit is not None:
+            assert self.kind == "ddim" and self.geo is None, "editing is built for the whole-latent DDIM engine"
+            assert noise_dropout == 0. and score_corrector is None, "an edit has no noise_dropout / score_corrector"
+            assert 1 <= edit.k <= self.n_steps and 0 <= edit.first_stage < self.num_stage, (edit.k, edit.first_stage)
         if self.kind == "dpm" and (noise_dropout > 0. or score_corrector is not None):
             raise NotImplementedError("the DPM-Solver loop is deterministic and has no hook between the denoiser and the update: "
                                       "noise_dropout / score_corrector are not built for it")
@@ -516,19 +563,26 @@ class SamplerEngine:
             raise refuse("score_corrector")
         o = SimpleNamespace(draw=self._host_draw(noise), seed=seed, sample0=sample0, log_every_t=log_every_t, callback=callback,
                             img_callback=img_callback, noise_dropout=float(noise_dropout), score_corrector=score_corrector,
-                            corrector_kwargs=dict(corrector_kwargs or {}), model=model, cond=cond, temps=None)
+                            corrector_kwargs=dict(corrector_kwargs or {}), model=model, cond=cond, temps=None, edit=edit,
+                            n=edit.k if edit is not None else self.n_steps)
+        o.row0 = self.n_steps - o.n
         with self._own_stream() as sp:
             ctx = self._context(cond, uncond)
             self.cfg_dev.fill_(self.cfg_scale)
-            self._init_x(x_T, o.draw, seed, sample0, sp)
+            if edit is not None:
+                self._bind_edit(edit, sp)
+            if edit is not None and edit.init == "z0":
+                self.x.copy_(self.z0)           # every stage noises its own window of this; the stages below first_stage keep it
+            else:
+                self._init_x(x_T, o.draw, seed, sample0, sp)
             x0_nchw = self._to_nchw(self.x, sp)
             o.inter = {"x_inter": [x0_nchw], "pred_x0": [x0_nchw]}
             t_loop = torch.from_numpy(self.t_loop.astype(np.int64)).to(self.dev)
             for s in range(self.num_stage):
-                if x_T is not None and s == 0:
+                if (x_T is not None and s == 0) if edit is None else s < edit.first_stage:
                     continue                 # ddim.py:150-152: "Auto adopt x_T into stage 0" (no denoising, no hand-off)
-                self._bind_stage(s, ctx, t_loop, sp)
-                (self._plms_stage if self.kind == "plms" else self._ddim_stage)(s, sp, o)
+                self._bind_stage(s, ctx, t_loop, sp, o.row0)
+                (self._plms_stage if self.kind == "plms" else self._edit_stage if edit is not None else self._ddim_stage)(s, sp, o)
                 levels = self.num_stage - s - 1
                 if levels > 0:
                     c0, c1 = sum(self.embed[:s]), sum(self.embed[:s + 1])
@@ -541,7 +595,7 @@ class SamplerEngine:
         return out, o.inter
 
     def _log(self, s, i, sp, o):
-        n, Cs = self.n_steps, sum(self.embed[:s + 1])
+        n, Cs = o.n, sum(self.embed[:s + 1])
         if o.callback:
             o.callback(i)
         if o.img_callback:
@@ -579,6 +633,90 @@ class SamplerEngine:
         key = ("dpm" if self.kind == "dpm" else "ddim_tape" if noise else "ddim", s)
         self._body(key, sp, lambda: [self._eval_ops(s), self._update_op(s, noise), 1])
         self._replay(key, self._unit_steps(o, GRAPH_STEPS), logged_at(n, o.log_every_t), sp, after_unit=log)
+
+    # ---- editing: img2img start and keep-mask inpainting in DDIM's loop ---------------------------------------------------------
+    def _bind_edit(self, ed, sp):
+        """This run's clean latent, stage masks and q_sample coefficients into the engine's fixed buffers (the captured bodies read them:
+        another z0 / mask replays the same graphs).  qtab row r = {sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t]} at the chain's
+        timestep of row r, gathered from the model's own float32 buffers."""
+        B, C, H, W = self.B, self.C, self.H, self.W
+        if not hasattr(self, "z0"):
+            self.z0 = torch.zeros_like(self.x)
+            self.qtab = torch.zeros(self.n_steps, 2, dtype=torch.float32, device=self.dev)
+            self.masks = [torch.zeros(B, H * W, dtype=torch.float32, device=self.dev) for _ in range(self.num_stage)]
+        z = ed.z0.to(self.dev, torch.float32).contiguous()
+        assert z.shape == (B, C, H, W), (tuple(z.shape), (B, C, H, W))
+        _relayout(self.b, sp, z, self.z0, B, H * W, C, 0)
+        t = torch.from_numpy(self.t_loop.astype(np.int64))
+        sa, sb = (v.detach().to("cpu", torch.float32)[t] for v in (ed.sqrt_ac, ed.sqrt_1mac))
+        self.qtab.copy_(torch.stack((sa, sb), dim=1))
+        if ed.masks is not None:
+            assert len(ed.masks) == self.num_stage
+            for dst, m in zip(self.masks, ed.masks):
+                assert m.shape == (B, 1, H, W), (tuple(m.shape), (B, 1, H, W))
+                dst.copy_(m.to(self.dev, torch.float32).reshape(B, H * W))
+
+    def _blend_op(self, s, window, masked, noise=None, clean=False):
+        """(KEEP_BLEND, FridoKeepBlend) on the engine's state: x <- q * m + (1 - m) * x on the channel window, q = q_sample(z0) at the device
+        step counter's row (clean: q = z0).  masked: stage s's mask, else m = 1.  noise: None -- Philox keyed by the device {seed, sample0},
+        draw = row + 1, stream EDIT_RNG_STREAM + s -- or (address, channels) of a host tape read by step index."""
+        kw = dict(x=self.x.data_ptr(), z0=self.z0.data_ptr(), mask=self.masks[s].data_ptr() if masked else None, B=self.B, HW=self.H * self.W,
+                  Cx=self.C, c0=window[0], c1=window[1], clean=int(clean))
+        if not clean:
+            kw.update(qtab=self.qtab.data_ptr(), step=self.step.data_ptr())
+            if noise is not None:
+                kw.update(noise=noise[0], noise_stride=self.B * self.H * self.W * noise[1], noise_C=noise[1])
+            else:
+                kw.update(rng_dev=self.rng.data_ptr(), rng_stream=EDIT_RNG_STREAM + s)
+        return KEEP_BLEND, _lib.STRUCTS["FridoKeepBlend"](**kw)
+
+    def _edit_stage(self, s, sp, o):
+        """One stage of an edit: the last o.n rows of DDIM's chain (the device counter starts at row0 = n_steps - o.n) with the blends of
+        csrc/edit.hip around them.
+          init "z0": the stage starts from q_sample(z0) on its window at the first row (one unmasked blend; frido.py:302-318 with
+                     ch_start: earlier stages clean, the stage's own channels noised -- the state the denoiser was trained on);
+          a mask:    before EVERY model evaluation (ddim.py:158-161) x <- q_sample(z0, t) * m + (1 - m) * x on the window: the step body is
+                     [blend, evaluation, update, +1].  Under init "z0" step 0 runs the plain body: its state already is that draw;
+          reimpose:  after the last step, before the hand-off, z0 itself goes back under the mask (a noise-free blend).
+          blend "reference": the window is [0, e_s), the frozen channels included (ddim.py:160-161 read literally).
+        Host noise ("torch" / a tape) is drawn per stage in the reference's order -- the start draw, then per step the blend's draw
+        (q_sample's randn_like), then the update's -- each (B, e_s, H, W), and uploaded to two tapes read by step index."""
+        ed, n, row0 = o.edit, o.n, o.row0
+        a, e = sum(self.embed[:s]), sum(self.embed[:s + 1])
+        window = (a, e) if ed.blend == "stage" else (0, e)
+        masked, start, tape = ed.masks is not None, ed.init == "z0", o.draw is not None
+        noise = bnoise = None
+        if tape:
+            shape, blends, updates = (self.B, e, self.H, self.W), [], []
+            first = o.draw(shape) if start else None
+            for i in range(n):
+                blends.append(o.draw(shape) if masked and not (start and i == 0) else first if i == 0 and start else torch.zeros(shape))
+                updates.append(o.draw(shape))
+            noise = self._upload_noise(s, updates, row0)
+            if start or masked:
+                bnoise = self._upload_noise(s, blends, row0, key=("blend", s))
+        else:
+            self.rng.copy_(torch.tensor([o.seed, o.sample0], dtype=torch.int64))
+        log = lambda i: self._log(s, i, sp, o)
+        if start:
+            self._prog([self._blend_op(s, window, False, bnoise)]).run(sp)
+        # blend "reference" rewrites the frozen channels in every step, and the stage's hoisted invariants (`pre`: the SPADE maps) are
+        # computed from them: its bodies recompute `pre` in front of every evaluation
+        ref = ed.blend == "reference"
+        form, pre = ("_tape" if tape else "") + ("_ref" if ref else ""), [list(self.stages[s].pre.ops)] if ref else []
+        key = plain = ("ddim" + form, s)
+        self._body(plain, sp, lambda: pre + [self._eval_ops(s), self._update_op(s, noise), 1])
+        i0 = 0
+        if masked:
+            key = ("edit" + form, s)
+            self._body(key, sp, lambda: [self._blend_op(s, window, True, bnoise)] + pre + [self._eval_ops(s), self._update_op(s, noise), 1])
+            if start:
+                self._go(self.graphs[plain], sp)
+                log(0)
+                i0 = 1
+        self._replay(key, self._unit_steps(o, GRAPH_STEPS), logged_at(n, o.log_every_t), sp, after_unit=log, n=n, i0=i0)
+        if masked and ed.reimpose:
+            self._prog([self._blend_op(s, window, True, clean=True)]).run(sp)
 
     def _plms_stage(self, s, sp, o):
         """plms.py:156-194,285-303: Heun-style first step (two denoiser calls), then Adams-Bashforth 2/3/4.  Two step bodies per stage serve

@@ -58,6 +58,18 @@ def cached_engine(rt, key, make):
     return cache[key]
 
 
+def edit_steps(S, t_start=None, strength=None):
+    """How many of the S steps an edit runs: exactly one of t_start (the integer itself, in [1, S]) and strength
+    (clamp(int(strength * S), 1, S)) is given."""
+    if (t_start is None) == (strength is None):
+        raise ValueError("edit: give exactly one of t_start (steps to run) and strength (the fraction of the S steps)")
+    if strength is not None:
+        return min(max(int(strength * S), 1), S)
+    if isinstance(t_start, bool) or not isinstance(t_start, (int, np.integer)) or not 1 <= t_start <= S:
+        raise ValueError(f"edit: t_start={t_start!r} must be an integer in [1, {S}]")
+    return int(t_start)
+
+
 class _SamplerBase:
     KIND = "ddim"
 
@@ -159,6 +171,82 @@ class _SamplerBase:
                            score_corrector=score_corrector, corrector_kwargs=corrector_kwargs, model=self.model)
         from . import autoplanes
         return autoplanes.run(self.model.model.diffusion_model, go, f"{type(self).__name__}.sample", noise=noise)
+
+    @torch.no_grad()
+    def edit(self, S, z0, conditioning=None, *, t_start=None, strength=None, keep_mask=None, init="z0", blend="stage", reimpose=True,
+             first_stage=0, num_stage=1, eta=0., x_T=None, temperature=1., unconditional_guidance_scale=1.,
+             unconditional_conditioning=None, noise="torch", seed=0, sample0=0, callback=None, img_callback=None, log_every_t=100,
+             verbose=True, replica=0, score_corrector=None, noise_dropout=0.):
+        """Edit the latent z0 (B, C, H, W) instead of sampling one: the LAST k of the S DDIM steps in every stage from `first_stage` on,
+        k = t_start or clamp(int(strength * S), 1, S).  Returns (samples, intermediates) like `sample`.  (Where S does not divide the model's
+        timesteps the uniform grid has more than S rows -- 7 at S = 6 of 1000 -- and k still counts from its end.)
+
+        init="z0" (img2img / SDEdit): every stage starts from q_sample of z0 at the chain's first timestep on the stage's own channels --
+        Frido's own multi-stage form (frido.py:302-318 with ch_start: earlier stages clean, the stage's channels noised), the state the
+        denoiser was trained on.  init="noise": the start is x_T, or a draw as in `sample`.
+        keep_mask (B, 1, H, W) in [0, 1], 1 = keep z0 (inpainting): before every denoiser evaluation
+        x <- q_sample(z0, t) * m + (1 - m) * x (ddim.py:158-161) with the stage's mask -- the mask's minimum over the stage's
+        2^(num_stage - 1 - s) blocks, so a coarse cell is kept only where all of it is; reimpose: after a stage's last step z0 itself is
+        put back under the mask.
+        blend="stage" (default) blends the stage's own channels [a_s, e_s).  blend="reference" blends [0, e_s), the literal reading of
+        ddim.py:160-161 where the reference does run (x_T given, so stage 0 is adopted and stage 1 has x0's channels): it re-noises the
+        frozen coarse channels in every step, which the stage's denoiser never saw in training and which the hand-off has already fixed,
+        so it is kept to pin the arithmetic and the draw order to the reference, not as the default.
+        Stages below first_stage keep the start state's channels (z0's, or x_T's under init="noise").
+        noise: "torch" / a tape draw per stage in the reference's order -- the start draw, then per step the blend's draw and the update's
+        draw, each (B, e_s, H, W); "philox": keyed by (seed, global sample index), the blend draws on streams of their own.
+        `sample(mask=, x0=)` stays refused; PLMS / DPM-Solver editing, split_input_params, score_corrector, noise_dropout and dict / list
+        conditionings are refused by name."""
+        no = lambda what: NotImplementedError(f"{type(self).__name__}.edit: {what} is not built for editing")
+        if self.KIND != "ddim":
+            raise no(f"{type(self).__name__} (editing runs in DDIM's loop: use DDIMSampler.edit)")
+        from . import patching
+        if patching.params_of(self.model) is not None:
+            raise no("split_input_params (the patch-wise mode)")
+        if score_corrector is not None:
+            raise no("score_corrector")
+        if noise_dropout:
+            raise no("noise_dropout")
+        if isinstance(conditioning, (dict, list)) or isinstance(unconditional_conditioning, (dict, list)):
+            raise no("a dict / list conditioning")
+        k = edit_steps(S, t_start, strength)
+        if init not in ("z0", "noise") or blend not in ("stage", "reference"):
+            raise ValueError(f"edit: init={init!r} ('z0' or 'noise'), blend={blend!r} ('stage' or 'reference')")
+        if not 0 <= first_stage < num_stage:
+            raise ValueError(f"edit: first_stage={first_stage} must name one of the {num_stage} stages that run")
+        if init == "noise" and keep_mask is None and x_T is None:
+            raise ValueError("edit: init='noise' with neither keep_mask nor x_T edits nothing -- that is sample()")
+        if init == "z0" and x_T is not None:
+            raise ValueError("edit: x_T is the start state of init='noise'; init='z0' starts from z0")
+        if not torch.is_tensor(z0) or z0.dim() != 4:
+            raise ValueError("edit: z0 is the (B, C, H, W) latent to edit")
+        B, shape = z0.shape[0], tuple(z0.shape[1:])
+        if keep_mask is not None:
+            if not torch.is_tensor(keep_mask) or tuple(keep_mask.shape) != (B, 1) + shape[1:]:
+                raise ValueError(f"edit: keep_mask must be {(B, 1) + shape[1:]}, got {tuple(getattr(keep_mask, 'shape', ()))}")
+            if keep_mask.device != z0.device:
+                raise ValueError(f"edit: keep_mask lives on {keep_mask.device}, z0 on {z0.device}")
+        if x_T is not None and tuple(x_T.shape) != (B,) + shape:
+            raise ValueError(f"edit: x_T must be {(B,) + shape}, got {tuple(x_T.shape)}")
+        mode = self._check_guidance(conditioning, unconditional_conditioning, unconditional_guidance_scale, B)
+        if not z0.is_cuda:
+            raise FridoHipError("edit(): z0 must live on the MI355X (there is no CPU path)")
+        self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+        if unconditional_guidance_scale != 1.:
+            assert unconditional_conditioning is not None
+        if verbose:
+            print(f"Data shape for DDIM editing is {(B, *shape)}, eta {eta}, the last {k} of {S} steps")
+        self.num_stage = num_stage
+        from .runtime import EditSpec, stage_masks
+        masks = stage_masks(keep_mask.float(), num_stage) if keep_mask is not None else None
+        spec = EditSpec(z0, k, self.model.sqrt_alphas_cumprod, self.model.sqrt_one_minus_alphas_cumprod, masks, init, blend, reimpose, first_stage)
+
+        def go(noise_src):
+            eng = self._engine(B, shape, mode, S, eta, unconditional_guidance_scale, num_stage, temperature, replica)
+            return eng.run(conditioning, unconditional_conditioning, x_T=x_T, noise=noise_src, seed=seed, sample0=sample0,
+                           log_every_t=log_every_t, callback=callback, img_callback=img_callback, model=self.model, edit=spec)
+        from . import autoplanes
+        return autoplanes.run(self.model.model.diffusion_model, go, f"{type(self).__name__}.edit", noise=noise)
 
 
 class DDIMSampler(_SamplerBase):

@@ -523,6 +523,37 @@ typedef struct FridoDpmStep {
     float* x0_hist;              /* [B*HW][nch], read on second-order rows, always written */
 } FridoDpmStep;
 
+/* ---- DDIM editing: the img2img start and the keep-mask blend of an inpainting loop (frido/models/diffusion/ddim.py:158-161 with
+ * q_sample, frido/models/diffusion/frido.py:302-318) ----
+ * Not an op kind: an exported launcher with a descriptor of its own (frido_keep_blend below), run eagerly or between frido_capture_begin and
+ * frido_capture_end.  One pass over the NHWC f32 state x[B][HW][Cx], in place, on the channel window [c0, c1); in fp32, every product and
+ * sum rounded on its own (no contraction):
+ *   q  = sa * z0[b][p][c] + sb * n
+ *   x' = q * m[b][p] + (1 - m[b][p]) * x
+ * Channels outside the window keep their bits (they are neither read nor written).  z0 [B][HW][Cx] is the clean latent, mask [B][HW] in
+ * [0, 1] (1 = keep z0); mask == NULL means m = 1 everywhere and x' = q, a pure q_sample (the SDEdit start).
+ * {sa, sb} = qtab[*step + row_offset]: qtab [rows][2] holds the model's own sqrt_alphas_cumprod[t] and sqrt_one_minus_alphas_cumprod[t]
+ * at the chain's timesteps (step NULL reads as 0).  clean = 1: q = z0 (sa = 1, sb = 0), no noise and no qtab are read -- a hard
+ * re-imposition of z0 under the mask.
+ * Noise, one form per launch:
+ *   tape:   noise != NULL, [step][B][HW][noise_C] read at row *step (NOT + row_offset: the layout of the DDIM update's tape), noise_stride
+ *           floats per row, tape channel c is state channel c (noise_C >= c1: "the channels reached so far");
+ *   Philox: noise == NULL, Philox4x32-10 + Box-Muller keyed by (seed, sample0 + b, draw = *step + row_offset + 1, rng_stream); rng_dev, an
+ *           optional device {seed, sample0}, overrides the two fields (graph replay).  Numbering of the draws: the window channel
+ *           j = c - c0 of pixel p is lane j & 3 of group p * ceil((c1 - c0) / 4) + (j >> 2) -- it depends on the pixel and the window only,
+ *           never on B or on the sample's place in the batch.  The sampling engine passes rng_stream = 64 + stage, disjoint from 0 (x_T)
+ *           and 1 .. num_stage (the updates' draws).
+ * Any B, HW, Cx and window; scalar accesses.  A non-finite x' raises FRIDO_STATUS_NONFINITE. */
+typedef struct FridoKeepBlend {
+    float* x; const float* z0; const float* mask;
+    const float* qtab; const int32_t* step;
+    const float* noise; int64_t noise_stride;
+    const int64_t* rng_dev; uint64_t seed; int64_t sample0;
+    int32_t B, HW, Cx, c0, c1, row_offset, noise_C, rng_stream, clean;
+} FridoKeepBlend;
+/* frido_sizeof_desc() code of a descriptor that belongs to no op kind */
+#define FRIDO_DESC_KEEP_BLEND 1001
+
 enum FridoOpKind {
     FRIDO_OP_GEMM = 1, FRIDO_OP_GN_STATS, FRIDO_OP_GN_APPLY, FRIDO_OP_LAYERNORM, FRIDO_OP_SOFTMAX,
     FRIDO_OP_GEGLU, FRIDO_OP_PACK, FRIDO_OP_RELAYOUT, FRIDO_OP_VQ, FRIDO_OP_SAMPLER_STEP,
@@ -619,6 +650,9 @@ int frido_vq_commit_loss(const FridoVqCommitLoss* d, frido_stream_t s);
 /* ---- the DPM-Solver++(2M) update (descriptor above); bad arguments return FRIDO_EINVAL before any device is touched ---- */
 int frido_dpm_step(const FridoDpmStep* d, frido_stream_t s);
 
+/* ---- the editing blend (descriptor above); bad arguments return FRIDO_EINVAL before any device is touched ---- */
+int frido_keep_blend(const FridoKeepBlend* d, frido_stream_t s);
+
 /* ---- timing on the launch stream (HIP events) ---- */
 int frido_event_create(void** ev);
 int frido_event_record(void* ev, frido_stream_t s);
@@ -635,7 +669,7 @@ int frido_abi_version(void);
  * A host that packs weights / operands itself (hi = round(v), lo = round(v - hi) in this format) asks here. */
 int frido_x3_plane_format(void);
 int frido_sizeof_op(void);             /* sizeof(FridoOp): checked by the ctypes mirror */
-int frido_sizeof_desc(int32_t kind);   /* sizeof of the descriptor struct of that op kind */
+int frido_sizeof_desc(int32_t kind);   /* sizeof of the descriptor struct of that op kind (or of FRIDO_DESC_KEEP_BLEND) */
 const char* frido_last_error(void);
 /* Sticky numerics status of the CURRENT device (r05): kernels cannot return errors, so operand producers and normalisation kernels
  * OR bits into a device word when they meet a value the arithmetic cannot represent, and this call reads it back (it synchronises
