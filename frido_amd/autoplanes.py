@@ -46,8 +46,6 @@ def run(module, call, what, noise=None):
     `noise` is passed through to call(): "philox" / "torch" / a callable / None."""
     if not config.auto_planes(getattr(module, "precision", None)) or module.planes != "f16":
         return call(noise)
-    if not hasattr(_lib.lib("f16"), "frido_status_poll"):        # an older build under FRIDO_LIB: no stream-ordered poll, r05 behaviour
-        return call(noise)
     rec = _Recorder(noise) if callable(noise) else None
     rng = torch.get_rng_state()                                   # noise="torch" / noise_dropout draw from the host generator
     _lib.status_poll("f16", clear=True)                           # earlier bits move to the host-side sticky word

@@ -702,7 +702,7 @@ class Builder:
     @staticmethod
     def _flash_ln_ok(d):
         L = _lib.lib()
-        return bool(L.frido_attn_flash_ln_supported(d)) if hasattr(L, "frido_attn_flash_ln_supported") else d in (256, 384)
+        return bool(L.frido_attn_flash_ln_supported(d))
 
     def v_transposed(self, x, ldx, wop, B, Nk, d, *, bias_ptr=None, out=None, x_off=0):
         """vT[z][d][Nk_pad] = (W_v @ x[z]^T): the value projection written transposed so that PV is an

@@ -345,6 +345,32 @@ def current_stream_ptr(device=None):
     return torch.cuda.current_stream(device).cuda_stream
 
 
+@contextlib.contextmanager
+def own_stream(owner, device):
+    """The block runs on `owner`'s own stream (owner._stream, created on first use; yields its handle), ordered after what the caller's
+    stream holds so far; the caller's stream waits for it when the block ends.  The host waits for nothing."""
+    if getattr(owner, "_stream", None) is None:
+        owner._stream = torch.cuda.Stream(device=device)
+    owner._stream.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(owner._stream):
+        yield owner._stream.cuda_stream
+    torch.cuda.current_stream(device).wait_stream(owner._stream)
+
+
+def lru_entry(cache, key, size, make, before_evict=None):
+    """cache[key] of a least-recently-used dict of at most `size` entries (most recent last): on a miss the oldest entries go first
+    (before_evict() ahead of each), then make() builds the new one."""
+    if key in cache:
+        cache[key] = cache.pop(key)
+    else:
+        while len(cache) >= size:
+            if before_evict is not None:
+                before_evict()
+            cache.pop(next(iter(cache)))
+        cache[key] = make()
+    return cache[key]
+
+
 def require_gpu(device):
     device = torch.device(device)
     if device.type != "cuda":

@@ -12,8 +12,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, config, holders, schedules
+from . import _lib, autoplanes, config, holders, runtime, schedules
 from ._lib import FridoHipError
+from .engine import current_stream_ptr, lru_entry
 
 try:  # pytorch-lightning is optional (absent in this image): keep the LightningModule base when it exists
     import pytorch_lightning as _pl
@@ -67,13 +68,20 @@ def instantiate_from_config_main(cfg, *args, **kwargs):
     return get_obj_from_str(cfg["target"])(*args, **_plain(cfg.get("params", dict())), **kwargs)
 
 
-def _no_cpu(what, device):
-    raise FridoHipError(f"{what}: tensors are on '{device}', but the Frido hot path runs only on an MI355X HIP device "
-                        "(move the model and its inputs with .cuda()); there is no CPU fallback")
+def _on_gpu(what, *things):
+    """Raises FridoHipError unless every tensor of `things`, and the first parameter of every module, is on a HIP device (anything else
+    among them -- None, a dict conditioning -- is passed over)."""
+    for t in things:
+        device = t.device if torch.is_tensor(t) else next(t.parameters()).device if isinstance(t, nn.Module) else None
+        if device is not None and device.type != "cuda":
+            raise FridoHipError(f"{what}: tensors are on '{device}', but the Frido hot path runs only on an MI355X HIP device "
+                                "(move the model and its inputs with .cuda()); there is no CPU fallback")
 
 
 class _Versioned:
-    """Mixin: drops compiled HIP plans whenever the module's weights change."""
+    """Mixin: drops compiled HIP plans whenever the module's weights change.  _what: the class's name in its errors.  _runtime: (class of
+    frido_amd.runtime, attribute holding its configuration) of the classes that run through runtime() -- the denoiser and the two first
+    stages; the text towers keep a bare Builder and set none."""
 
     def _init_versioning(self):
         self._rt = None
@@ -82,6 +90,18 @@ class _Versioned:
 
     def invalidate(self):
         self._rt = None
+
+    def runtime(self, precision=None):
+        """The compiled runtime of the module's weights on their device, at `precision` (default: the module's, then config.PRECISION).
+        Only for classes that set _runtime."""
+        cls, cfg = self._runtime
+        dev = next(self.parameters()).device
+        key = (str(dev), precision or self.precision or config.PRECISION)
+        if self._rt is None or self._rt_key != key:
+            _on_gpu(self._what, self)
+            self._rt = getattr(runtime, cls)(self, getattr(self, cfg), dev, key[1])
+            self._rt_key = key
+        return self._rt
 
     # which build of the library the module runs on (_lib.use_planes); the default precision keyword lets autoplanes.run() change it
     planes = property(lambda self: config.planes(getattr(self, "precision", None)))
@@ -93,6 +113,8 @@ class _Versioned:
 
 # ---- denoiser (frido/modules/diffusionmodules/pyunet.py:447-950) -------------------------------------
 class PyUNetModel(_Versioned, nn.Module):
+    _what, _runtime = "PyUNetModel", ("DenoiserRuntime", "cfg")
+
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks, attention_resolutions,
                  dropout=0, channel_mult=(1, 2, 4, 8), conv_resample=True, dims=2, num_classes=None, use_checkpoint=False,
                  use_fp16=False, num_heads=-1, num_head_channels=-1, num_heads_upsample=-1, use_scale_shift_norm=False,
@@ -146,17 +168,6 @@ class PyUNetModel(_Versioned, nn.Module):
         self.arch = holders.build_unet_params(self, self.cfg)
         self._init_versioning()
 
-    def runtime(self, precision=None):
-        from .runtime import DenoiserRuntime
-        dev = next(self.parameters()).device
-        key = (str(dev), precision or self.precision or config.PRECISION)
-        if self._rt is None or self._rt_key != key:
-            if dev.type != "cuda":
-                _no_cpu("PyUNetModel", dev)
-            self._rt = DenoiserRuntime(self, self.cfg, dev, key[1])
-            self._rt_key = key
-        return self._rt
-
     def forward(self, x, timesteps=None, context=None, y=None, stage=None, **kwargs):
         # pyunet.py:877-879 asserts (y is not None) == (num_classes is not None)
         if y is not None and self.num_classes is None:
@@ -174,11 +185,9 @@ class PyUNetModel(_Versioned, nn.Module):
                 assert y.shape == (x.shape[0],), "y: one class index per sample (pyunet.py:887)"
             else:
                 assert y.shape == (x.shape[0], self.num_classes), "y: [B, num_classes] for the Linear label embedding"
-        if not x.is_cuda:
-            _no_cpu("PyUNetModel.forward", x.device)
+        _on_gpu("PyUNetModel.forward", x)
         if self.num_stage > 1 and not isinstance(stage, int):
             stage = int(stage)
-        from . import autoplanes
         return autoplanes.run(self, lambda _n: self.runtime().forward(x, timesteps, context, stage, y=y), "PyUNetModel.forward")
 
 
@@ -200,18 +209,19 @@ class _Quantizer(nn.Module):
         self.embedding = holders.Emb(n_e, e_dim)
 
 
-class VQModelInterface(_Versioned, _Base):
-    def __init__(self, embed_dim, channel_range=[], edconfig=None, ddconfig=None, lossconfig=None, n_embed=None,
-                 fusion="concat", ckpt_path=None, ignore_keys=[], image_key="image", colorize_nlabels=None, monitor=None,
-                 remap=None, sane_index_shape=False, on_vit=[], use_aux_loss=False, unsample_type="nearest",
-                 quant_beta=0.25, legacy=True, init_normal=False, precision=None):
+class _FirstStage(_Versioned, _Base):
+    """What the two MS-VQGAN classes share: the holders of the reference's parameter / state_dict key set, the attributes FridoDiffusion
+    and the runtime read, the no-op loss, the checkpoint load.  A subclass refuses what it does not build before it calls this constructor
+    and adds its own attributes after it."""
+    _runtime = ("DecoderRuntime", "vq_cfg")
+
+    def __init__(self, edconfig, ddconfig, n_embed, embed_dim, quant_beta, *, fusion, ckpt_path, ignore_keys, image_key, monitor, precision):
         super().__init__()
         edconfig, ddconfig = _plain(edconfig), _plain(ddconfig)
         embed_dim, n_embed = list(embed_dim), list(n_embed)
-        assert fusion == "concat" and remap is None, "only the 'concat' fusion without remap is used by Frido configs"
         assert len(n_embed) == edconfig["multiscale"] == len(embed_dim), "multiscale mode. dim of n_embed is incorrect."
         self.image_key, self.fusion = image_key, fusion
-        self.embed_dim, self.n_embed, self.channel_range = embed_dim, n_embed, channel_range
+        self.embed_dim, self.n_embed = embed_dim, n_embed
         self.edconfig, self.ddconfig = edconfig, ddconfig
         self.vq_cfg = dict(embed_dim=embed_dim, n_embed=n_embed, edconfig=edconfig, ddconfig=ddconfig)
         self.precision = precision
@@ -221,6 +231,8 @@ class VQModelInterface(_Versioned, _Base):
         self.encoder.num_resolutions = len(edconfig["ch_mult"])
         self.encoder.multiscale = edconfig["multiscale"]
         self.encoder.resolution = edconfig["resolution"]
+        # lossconfig: VQLPIPSWithDiscriminator is LPIPS (VGG weights: a download) + a PatchGAN trained by the backward pass -- whatever
+        # the target, the module holds the no-op loss
         self.loss = DummyLoss()
         nres = len(edconfig["ch_mult"])
         self.res_list = [edconfig["resolution"] / 2 ** (nres - i - 1) for i in range(edconfig["multiscale"])]
@@ -237,27 +249,27 @@ class VQModelInterface(_Versioned, _Base):
                 del sd[k]
         self.load_state_dict(sd, strict=False)
 
-    def runtime(self):
-        from .runtime import DecoderRuntime
-        dev = next(self.parameters()).device
-        key = (str(dev), self.precision or config.PRECISION)
-        if self._rt is None or self._rt_key != key:
-            if dev.type != "cuda":
-                _no_cpu("VQModelInterface", dev)
-            self._rt = DecoderRuntime(self, self.vq_cfg, dev, key[1])
-            self._rt_key = key
-        return self._rt
+
+class VQModelInterface(_FirstStage):
+    _what = "VQModelInterface"
+
+    def __init__(self, embed_dim, channel_range=[], edconfig=None, ddconfig=None, lossconfig=None, n_embed=None,
+                 fusion="concat", ckpt_path=None, ignore_keys=[], image_key="image", colorize_nlabels=None, monitor=None,
+                 remap=None, sane_index_shape=False, on_vit=[], use_aux_loss=False, unsample_type="nearest",
+                 quant_beta=0.25, legacy=True, init_normal=False, precision=None):
+        assert fusion == "concat" and remap is None, "only the 'concat' fusion without remap is used by Frido configs"
+        super().__init__(edconfig, ddconfig, n_embed, embed_dim, quant_beta, fusion=fusion, ckpt_path=ckpt_path, ignore_keys=ignore_keys,
+                         image_key=image_key, monitor=monitor, precision=precision)
+        self.channel_range = channel_range
 
     @torch.no_grad()
     def decode(self, h_in, force_not_quantize=False, return_code=False, inv_scale=None, to_uint8=False, force_codes=None):
         """msvqgan.py:376-399.  Returns dec (B,3,H,W) [and per-scale code lists when return_code]; to_uint8 (True / "np" /
         "pil") returns the (B,H,W,3) uint8 image of scripts/sample_diffusion.py:115-121 (custom_to_np) or :103-113
         (custom_to_pil) straight from the epilogue of the decoder's last convolution."""
-        if not h_in.is_cuda:
-            _no_cpu("VQModelInterface.decode", h_in.device)
+        _on_gpu("VQModelInterface.decode", h_in)
         # force_not_quantize: accepted and IGNORED, exactly like the reference (msvqgan.py:376-399 never reads the flag: the
         # multi-scale decode always quantises)
-        from . import autoplanes
         out = autoplanes.run(self, lambda _n: self.runtime().decode(h_in, inv_scale=inv_scale, return_code=return_code, to_uint8=to_uint8,
                                                                     force_codes=force_codes), "VQModelInterface.decode")
         if return_code:
@@ -268,14 +280,12 @@ class VQModelInterface(_Versioned, _Base):
     @torch.no_grad()
     def encode(self, x, scale=None):
         """msvqgan.py:326-374: image (B,3,H,W) -> pre-quant multi-scale latent, channels [coarse .. fine]."""
-        if not x.is_cuda:
-            _no_cpu("VQModelInterface.encode", x.device)
+        _on_gpu("VQModelInterface.encode", x)
         assert len(self.channel_range) != 2, "channel_range slicing is not used by any shipped config"
-        from . import autoplanes
         return autoplanes.run(self, lambda _n: self.runtime().encode(x, scale=scale), "VQModelInterface.encode")
 
 
-class MSFPNVQModel(_Versioned, _Base):
+class MSFPNVQModel(_FirstStage):
     """taming/models/msvqgan.py:16-318: the MS-VQGAN as a model of its own -- what `main.py -t False` runs on configs/msvqgan/*.yaml.
     Where VQModelInterface hands the diffusion model the PRE-quant latent, this class returns what the tokenizer itself computes: the
     quantised multi-scale latent, the codes of every scale and the codebook loss (encode), an image from an already quantised latent
@@ -285,66 +295,32 @@ class MSFPNVQModel(_Versioned, _Base):
     nearest-upsampled to the finest grid -- the OPPOSITE of VQModelInterface.encode's [coarse .. fine].
     Same parameter / state_dict key set as the reference's class; no backward pass, no LPIPS / PatchGAN loss module."""
 
+    _what = "MSFPNVQModel"
+
     def __init__(self, edconfig, ddconfig, lossconfig, n_embed, embed_dim, fusion="concat", ckpt_path=None, ignore_keys=[],
                  image_key="image", colorize_nlabels=None, monitor=None, remap=None, sane_index_shape=False, on_vit=[],
                  use_aux_loss=False, unsample_type="nearest", quant_beta=0.25, legacy=True, init_normal=False, precision=None):
-        super().__init__()
-        edconfig, ddconfig = _plain(edconfig), _plain(ddconfig)
-        embed_dim, n_embed = list(embed_dim), list(n_embed)
         if remap is not None:
             raise NotImplementedError("remap: the quantiser's index remapping (quantize.py:229-241) is not built; no shipped config sets it")
         if fusion != "concat":
             raise NotImplementedError(f"fusion={fusion!r}: only the 'concat' fusion of the scales is built (msvqgan.py:59-66; every shipped config)")
-        if edconfig.get("double_z") or ddconfig.get("double_z"):
+        if _plain(edconfig).get("double_z") or _plain(ddconfig).get("double_z"):
             raise NotImplementedError("double_z=True: a quantised model has no use for the doubled moments (every shipped config sets double_z: False)")
         if colorize_nlabels is not None:
             raise NotImplementedError("colorize_nlabels: the random `colorize` projection of segmentation inputs (to_rgb, msvqgan.py:311-317) is not built")
-        assert len(n_embed) == edconfig["multiscale"], "multiscale mode. dim of n_embed is incorrect."
-        assert len(n_embed) == len(embed_dim), "multiscale mode. dim of n_embed is incorrect."
-        self.image_key, self.fusion = image_key, fusion
-        self.embed_dim, self.n_embed = embed_dim, n_embed
+        super().__init__(edconfig, ddconfig, n_embed, embed_dim, quant_beta, fusion=fusion, ckpt_path=ckpt_path, ignore_keys=ignore_keys,
+                         image_key=image_key, monitor=monitor, precision=precision)
+        self.vq_cfg.update(quant_beta=float(quant_beta), legacy=bool(legacy))
+        for q in self.ms_quantize:
+            q.legacy, q.sane_index_shape = legacy, sane_index_shape
         self.use_aux_loss, self.unsample_type = use_aux_loss, unsample_type
         self.sane_index_shape, self.quant_beta, self.legacy = sane_index_shape, quant_beta, legacy
-        self.edconfig, self.ddconfig = edconfig, ddconfig
-        self.vq_cfg = dict(embed_dim=embed_dim, n_embed=n_embed, edconfig=edconfig, ddconfig=ddconfig, quant_beta=float(quant_beta),
-                           legacy=bool(legacy))
-        self.precision = precision
-        holders.build_msvqgan_params(self, edconfig, ddconfig, n_embed, embed_dim)
-        for i, q in enumerate(self.ms_quantize):
-            q.n_e, q.e_dim, q.beta, q.legacy, q.sane_index_shape = n_embed[i], embed_dim[i], quant_beta, legacy, sane_index_shape
-        self.encoder.num_resolutions = len(edconfig["ch_mult"])
-        self.encoder.multiscale = edconfig["multiscale"]
-        self.encoder.resolution = edconfig["resolution"]
-        # lossconfig: VQLPIPSWithDiscriminator is LPIPS (VGG weights: a download) + a PatchGAN trained by the backward pass -- whatever
-        # the target, the module holds the no-op loss (like VQModelInterface)
-        self.loss = DummyLoss()
-        nres = len(edconfig["ch_mult"])
-        self.res_list = [edconfig["resolution"] / 2 ** (nres - i - 1) for i in range(edconfig["multiscale"])]
-        if monitor is not None:
-            self.monitor = monitor
-        self._init_versioning()
-        if ckpt_path is not None:
-            self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
-
-    init_from_ckpt = VQModelInterface.init_from_ckpt
-
-    def runtime(self):
-        from .runtime import DecoderRuntime
-        dev = next(self.parameters()).device
-        key = (str(dev), self.precision or config.PRECISION)
-        if self._rt is None or self._rt_key != key:
-            if dev.type != "cuda":
-                _no_cpu("MSFPNVQModel", dev)
-            self._rt = DecoderRuntime(self, self.vq_cfg, dev, key[1])
-            self._rt_key = key
-        return self._rt
 
     def _check_image(self, x, what):
         if x.shape[1] > 3:
             raise NotImplementedError(f"{what}: inputs with more than 3 channels (segmentation maps through to_rgb's random `colorize` "
                                       "projection, msvqgan.py:283-287,311-317) are not built")
-        if not x.is_cuda:
-            _no_cpu(what, x.device)
+        _on_gpu(what, x)
 
     def _info(self, idx, B, h, w):
         """msvqgan.py:121,142-143 with VectorQuantizer2's (perplexity, min_encodings, min_encoding_indices) = (None, None, idx)."""
@@ -359,7 +335,6 @@ class MSFPNVQModel(_Versioned, _Base):
         reference's z + (z_q - z) in fp32; emb_loss: 0-d f32, the scales' losses added coarse to fine; info_ms[2]: int64 codes per scale,
         coarse first."""
         self._check_image(x, "MSFPNVQModel.encode")
-        from . import autoplanes
         quant, loss, idx = autoplanes.run(self, lambda _n: self.runtime().encode_quant(x), "MSFPNVQModel.encode")
         return quant, loss, self._info(idx, quant.shape[0], quant.shape[2], quant.shape[3])
 
@@ -367,9 +342,7 @@ class MSFPNVQModel(_Versioned, _Base):
     def decode(self, quant, to_uint8=False):
         """msvqgan.py:156-159: post_quant_conv + decoder on an already quantised [fine .. coarse] latent -- NO VQ lookup (that is
         VQModelInterface.decode).  to_uint8 as on VQModelInterface.decode."""
-        if not quant.is_cuda:
-            _no_cpu("MSFPNVQModel.decode", quant.device)
-        from . import autoplanes
+        _on_gpu("MSFPNVQModel.decode", quant)
         return autoplanes.run(self, lambda _n: self.runtime().decode_quant(quant.contiguous().float(), to_uint8=to_uint8), "MSFPNVQModel.decode")
 
     def decode_code(self, code_b):
@@ -387,7 +360,6 @@ class MSFPNVQModel(_Versioned, _Base):
         """(what forward returns, quant)."""
         self._check_image(x, "MSFPNVQModel.forward")
         aux = bool(self.use_aux_loss)
-        from . import autoplanes
         dec, quant, diff, idx = autoplanes.run(self, lambda _n: self.runtime().reconstruct(x, aux=aux), "MSFPNVQModel.forward")
         info = self._info(idx, quant.shape[0], quant.shape[2], quant.shape[3])
         if aux:
@@ -448,7 +420,6 @@ class MSFPNVQModel(_Versioned, _Base):
         if len(self.embed_dim) >= 2:
             # (the reference encodes x a second time here, msvqgan.py:294: the same quant)
             groups = [(sum(self.embed_dim[:i]), sum(self.embed_dim[:i + 1])) for i in range(len(self.embed_dim))]
-            from . import autoplanes
             recs = autoplanes.run(self, lambda _n: self.runtime().decode_quant(quant, groups=groups), "MSFPNVQModel.log_images")
             B = x.shape[0]
             for i, (c0, c1) in enumerate(groups):
@@ -463,20 +434,51 @@ def _cached_plan(cache, key, builder, make):
     """LRU of compiled plans on one Builder.  A plan is built inside `persist_scope()`, so its persistent buffers (V^T operands,
     token / output tensors' companions) belong to the cache entry: evicting the least-recently-used shape frees their HBM
     instead of pinning one set per batch size ever seen.  The packed weights stay shared in the builder."""
-    if key in cache:
-        cache[key] = cache.pop(key)          # most recently used last
-        return cache[key][0]
-    while len(cache) >= PLAN_CACHE_SIZE:
-        cache.pop(next(iter(cache)))
-    with builder.persist_scope() as owned:
-        plan = make()
-    cache[key] = (plan, owned)
-    return plan
+    def build():
+        with builder.persist_scope() as owned:
+            return make(), owned
+    return lru_entry(cache, key, PLAN_CACHE_SIZE, build)[0]
 
 
 # ---- cond stage (frido/modules/encoders/modules.py:85-114) ---------------------------------------------
-class BERTEmbedder(_Versioned, nn.Module):
+class _TextTower(_Versioned, nn.Module):
+    """A text encoder on the HIP engine: one Builder over the weights (`_rt`) and an LRU of compiled plans per (batch, tokens) shape
+    (`_plans`).  A subclass supplies _tokens(text) -> ids, _make_plan(B, n) and, where a plan has per-call inputs beside the ids,
+    _bind(plan, tokens)."""
+
+    def _init_versioning(self):
+        super()._init_versioning()
+        self._plans = {}
+
+    def invalidate(self):
+        self._rt = None
+        self._plans = {}
+
+    def _bind(self, plan, tokens):
+        pass
+
+    @torch.no_grad()
+    @_lib.with_planes
+    def _run(self, text):
+        """(the plan of the tokens' shape after its program ran on them, the ids on the device)."""
+        tokens = self._tokens(text)
+        _on_gpu(self._what, self)
+        dev = next(self.parameters()).device
+        tokens = tokens.to(dev).long()
+        B, n = tokens.shape
+        self._check_length(n)
+        if self._rt is None:
+            self._rt = runtime.module_builder(self, dev, self.precision)
+        plan = _cached_plan(self._plans, (B, n), self._rt, lambda: self._make_plan(B, n))
+        plan.tokens.copy_(tokens.reshape(-1))
+        self._bind(plan, tokens)
+        plan.prog.run(current_stream_ptr(dev))
+        return plan, tokens
+
+
+class BERTEmbedder(_TextTower):
     """Token ids -> x-transformer encoder embeddings [B, n, n_embed] on the HIP engine."""
+    _what = "BERTEmbedder"
 
     def __init__(self, n_embed, n_layer, vocab_size=30522, max_seq_len=77, device="cuda", use_tokenizer=True,
                  embedding_dropout=0.0, cond_key="", precision=None, vocab_file=None):
@@ -488,38 +490,22 @@ class BERTEmbedder(_Versioned, nn.Module):
         self.cond_key, self.precision = cond_key, precision
         holders.build_bert_params(self, n_embed, n_layer, vocab_size, max_seq_len)
         self._init_versioning()
-        self._plans = {}
 
-    def invalidate(self):
-        self._rt = None
-        self._plans = {}
-
-    planes = property(lambda self: config.planes(self.precision))      # which build of the library (_lib.use_planes)
-
-    @torch.no_grad()
-    @_lib.with_planes
-    def forward(self, text, return_token=False):
+    def _tokens(self, text):
         tokens = text[self.cond_key] if self.cond_key != "" else text
-        if not torch.is_tensor(tokens):       # captions as strings (use_tokenizer=True configs): encoders/modules.py:63-64,99-104
-            tokens = self._tokenize(tokens)
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            _no_cpu("BERTEmbedder", dev)
-        tokens = tokens.to(dev).long()
-        B, n = tokens.shape
+        # captions as strings (use_tokenizer=True configs): encoders/modules.py:63-64,99-104
+        return tokens if torch.is_tensor(tokens) else self._tokenize(tokens)
+
+    def _check_length(self, n):
         assert n <= self.max_seq_len
-        from .builder import Builder
+
+    def _make_plan(self, B, n):
         from .bert_plan import BertPlan
-        from .engine import current_stream_ptr, require_gpu
-        from .runtime import _weights_of
-        if self._rt is None:
-            require_gpu(dev)
-            self._rt = Builder(dev, config.nsplit(self.precision), _weights_of(self, dev), planes=config.planes(self.precision))
-        plan = _cached_plan(self._plans, (B, n), self._rt, lambda: BertPlan(self._rt, B=B, n=n, dim=self.n_embed, depth=self.n_layer,
-                                                                            vocab=self.vocab_size))
-        plan.tokens.copy_(tokens.reshape(-1))
-        plan.prog.run(current_stream_ptr(dev))
-        z = plan.out.view(B, n, self.n_embed).clone()
+        return BertPlan(self._rt, B=B, n=n, dim=self.n_embed, depth=self.n_layer, vocab=self.vocab_size)
+
+    def forward(self, text, return_token=False):
+        plan, tokens = self._run(text)
+        z = plan.out.view(*tokens.shape, self.n_embed).clone()
         return (z, tokens) if return_token else z
 
     def encode(self, text):
@@ -555,7 +541,7 @@ class BERTEmbedder(_Versioned, nn.Module):
         return enc["input_ids"]
 
 
-class FrozenCLIPTextEmbedder(_Versioned, nn.Module):
+class FrozenCLIPTextEmbedder(_TextTower):
     """cond_stage_config.target of configs/frido/t2i/frido_f16f8_coco_clip.yaml:80 (reference:
     frido/modules/encoders/modules.py:188-219): the text tower of OpenAI CLIP -> ONE L2-normalised embedding per caption,
     `encode` adds the token axis and repeats it n_repeat times.  The tower runs on the HIP engine (clip_plan.ClipTextPlan);
@@ -565,6 +551,8 @@ class FrozenCLIPTextEmbedder(_Versioned, nn.Module):
     $FRIDO_CLIP_BPE (a local bpe_simple_vocab_16e6.txt.gz: frido_amd/tokenizers.py ClipBPETokenizer), pass `tokenizer=` (any
     callable list[str] -> LongTensor [B, 77]) or install `clip`; without any of them a clear error is raised at encode time.
     `arch` overrides the (embed_dim, context_length, vocab, width, heads, layers) of `version` (tests use a reduced tower)."""
+
+    _what = "FrozenCLIPTextEmbedder"
 
     def __init__(self, version="ViT-L/14", device="cuda", max_length=77, n_repeat=1, normalize=True, arch=None, tokenizer=None,
                  precision=None, bpe_path=None):
@@ -581,11 +569,6 @@ class FrozenCLIPTextEmbedder(_Versioned, nn.Module):
         self.arch = tuple(arch)
         holders.build_clip_text_params(self, *self.arch)
         self._init_versioning()
-        self._plans = {}
-
-    def invalidate(self):
-        self._rt = None
-        self._plans = {}
 
     def freeze(self):
         for p in self.parameters():
@@ -611,38 +594,34 @@ class FrozenCLIPTextEmbedder(_Versioned, nn.Module):
                 "token ids ([B, 77] int64), a tokenizer= callable, or the finished "
                 "[B, n_repeat, embed_dim] embedding to the sampler as `conditioning`") from None
 
-    planes = property(lambda self: config.planes(self.precision))
+    def _check_length(self, n):
+        assert n <= self.arch[1], f"{n} tokens > context length {self.arch[1]}"
 
-    @torch.no_grad()
-    @_lib.with_planes
-    def forward(self, text):
-        tokens = self._tokens(text)
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            _no_cpu("FrozenCLIPTextEmbedder", dev)
-        tokens = tokens.to(dev).long()
-        B, n = tokens.shape
-        embed_dim, ctx, vocab, width, heads, layers = self.arch
-        assert n <= ctx, f"{n} tokens > context length {ctx}"
-        from .builder import Builder
+    def _make_plan(self, B, n):
         from .clip_plan import ClipTextPlan
-        from .engine import current_stream_ptr, require_gpu
-        from .runtime import _weights_of
-        if self._rt is None:
-            require_gpu(dev)
-            self._rt = Builder(dev, config.nsplit(self.precision), _weights_of(self, dev), planes=config.planes(self.precision))
-        plan = _cached_plan(self._plans, (B, n), self._rt, lambda: ClipTextPlan(self._rt, B=B, n=n, width=width, layers=layers, heads=heads,
-                                                                                vocab=vocab, embed_dim=embed_dim, normalize=self.normalize))
-        plan.tokens.copy_(tokens.reshape(-1))
-        plan.eot_rows.copy_(tokens.argmax(dim=-1) + torch.arange(B, device=dev) * n)      # clip/model.py: the EOT token has the highest id
-        plan.prog.run(current_stream_ptr(dev))
-        return plan.out.clone()
+        embed_dim, _, vocab, width, heads, layers = self.arch
+        return ClipTextPlan(self._rt, B=B, n=n, width=width, layers=layers, heads=heads, vocab=vocab, embed_dim=embed_dim,
+                            normalize=self.normalize)
+
+    def _bind(self, plan, tokens):
+        B, n = tokens.shape
+        plan.eot_rows.copy_(tokens.argmax(dim=-1) + torch.arange(B, device=tokens.device) * n)      # clip/model.py: the EOT token has the highest id
+
+    def forward(self, text):
+        return self._run(text)[0].out.clone()
 
     def encode(self, text):
         z = self(text)
         if z.ndim == 2:
             z = z[:, None, :]
         return z.expand(-1, self.n_repeat, -1).contiguous()      # repeat(z, 'b 1 d -> b k d', k=n_repeat)
+
+
+def _first(cond, n):
+    """The conditioning cut to the batch (frido.py:1316-1320, 1429-1433): the first n rows of a tensor, or of every tensor of a list."""
+    if cond is None or isinstance(cond, dict):
+        return cond
+    return [c[:n] for c in cond] if isinstance(cond, list) else cond[:n]
 
 
 # ---- EMA shadow (frido/modules/ema.py) ---------------------------------------------------------------
@@ -893,8 +872,7 @@ class FridoDiffusion(_Base):
         from .runtime import patch_fold, patch_unfold
         B, _, H, W = x_noisy.shape
         geo = patching.geometry(patch, H, W, patching.MODEL, x_noisy.device)      # raises for a geometry the reference cannot stitch
-        if not x_noisy.is_cuda:
-            _no_cpu("FridoDiffusion.apply_model", x_noisy.device)
+        _on_gpu("FridoDiffusion.apply_model", x_noisy)
         unet = self.model.diffusion_model
         # the builder only launches layout changes and the two patch kernels, which are the same code in both builds of the library: should
         # the automatic plane selection move the denoiser to another runtime during the forward below, folding on this one is still right
@@ -927,9 +905,7 @@ class FridoDiffusion(_Base):
                 raise patching.refuse("return_code / force_codes (the reference's patch-wise decode returns the image only)")
             fs = self.first_stage_model
             geo = patching.geometry(patch, z_in.shape[2], z_in.shape[3], patching.DECODE, z_in.device)
-            if not z_in.is_cuda:
-                _no_cpu("FridoDiffusion.decode_first_stage", z_in.device)
-            from . import autoplanes
+            _on_gpu("FridoDiffusion.decode_first_stage", z_in)
             return autoplanes.run(fs, lambda _n: fs.runtime().decode_patches(z_in, geo, inv_scale=inv, to_uint8=to_uint8),
                                   "FridoDiffusion.decode_first_stage")
         return self.first_stage_model.decode(z_in, return_code=return_code, inv_scale=inv, to_uint8=to_uint8,
@@ -946,9 +922,7 @@ class FridoDiffusion(_Base):
             patch["original_image_size"] = x.shape[-2:]
             fs = self.first_stage_model
             geo = patching.geometry(patch, x.shape[2], x.shape[3], patching.ENCODE, x.device)
-            if not x.is_cuda:
-                _no_cpu("FridoDiffusion.encode_first_stage", x.device)
-            from . import autoplanes
+            _on_gpu("FridoDiffusion.encode_first_stage", x)
             return autoplanes.run(fs, lambda _n: fs.runtime().encode_patches(x, geo), "FridoDiffusion.encode_first_stage")
         return self.first_stage_model.encode(x)
 
@@ -1075,8 +1049,7 @@ class FridoDiffusion(_Base):
     def _anc_update(self, x, c, t, stage, clip_denoised, score_corrector, corrector_kwargs, noise=None, with_noise=False, temperature=1.,
                     seed=0, sample0=0):
         """Denoiser forward + ONE launch of the ancestral update kernel per distinct timestep: (x' or the posterior mean, x0)."""
-        if not x.is_cuda:
-            _no_cpu("FridoDiffusion.p_sample", x.device)
+        _on_gpu("FridoDiffusion.p_sample", x)
         from .runtime import ancestral_step
         stage = int(stage)
         start, end = sum(self.embed_dim_list[:stage]), sum(self.embed_dim_list[:stage + 1])
@@ -1112,8 +1085,7 @@ class FridoDiffusion(_Base):
         worth, repeated), times temperature, then the dropout mask; a callable shape -> tensor replays a tape; "philox" draws in the kernel,
         keyed by (seed, sample0 + b, num_timesteps - t, stage) -- the loops' key, so this call reproduces their draw at (t, stage)."""
         self._anc_refuse(c, quantize_denoised, return_codebook_ids)
-        if not x.is_cuda:
-            _no_cpu("FridoDiffusion.p_sample", x.device)
+        _on_gpu("FridoDiffusion.p_sample", x)
         nz = None
         if noise == "philox":
             if noise_dropout > 0. or repeat_noise:
@@ -1133,17 +1105,15 @@ class FridoDiffusion(_Base):
     def _anc_loop(self, cond, shape, T, what, *, noise, seed, sample0, collect, temperature=1., **kw):
         """The loop on the SamplerEngine (kind="ddpm"): cached per (batch, latent shape, conditioning mode, T, clip, temperature) next to the
         DDIM / PLMS engines of the denoiser, the whole call under the automatic plane selection."""
-        from . import autoplanes, samplers
+        from . import samplers
         from .runtime import SamplerEngine
         unet = self.model.diffusion_model
         B, C, H, W = (int(v) for v in shape)
         if isinstance(cond, list):
             raise NotImplementedError("list conditionings: pass the cross-attention conditioning tensor or the class labels")
-        if cond is not None and not isinstance(cond, dict) and not cond.is_cuda:
-            _no_cpu(what, cond.device)
+        _on_gpu(what, cond)
         mode = samplers.check_conditioning(unet, cond, B, name="cond")
-        if next(unet.parameters()).device.type != "cuda":
-            _no_cpu(what, next(unet.parameters()).device)
+        _on_gpu(what, unet)
         clip = bool(self.clip_denoised)
         temp_key = float(temperature) if noise == "philox" else 1.0
 
@@ -1172,8 +1142,7 @@ class FridoDiffusion(_Base):
             shape = [batch_size] + list(shape)
         else:
             batch_size = shape[0]
-        if cond is not None and not isinstance(cond, dict):
-            cond = [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+        cond = _first(cond, batch_size)
         T = self.num_timesteps if start_T is None else min(self.num_timesteps, start_T)
         return self._anc_loop(cond, shape, T, "FridoDiffusion.progressive_denoising", noise=noise, seed=seed, sample0=sample0, collect="x0",
                               temperature=temperature, x_T=x_T, log_every_t=log_every_t, callback=callback, img_callback=img_callback,
@@ -1202,8 +1171,7 @@ class FridoDiffusion(_Base):
         """frido.py:1420-1437.  Like the reference, only the named arguments reach p_sample_loop -- plus noise / seed / sample0 from kwargs."""
         if shape is None:
             shape = (batch_size, self.channels, self.image_size, self.image_size)
-        if cond is not None and not isinstance(cond, dict):
-            cond = [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+        cond = _first(cond, batch_size)
         extra = {k: kwargs[k] for k in ("noise", "seed", "sample0") if k in kwargs}
         return self.p_sample_loop(cond, shape, return_intermediates=return_intermediates, x_T=x_T, verbose=verbose, timesteps=timesteps,
                                   quantize_denoised=quantize_denoised, mask=mask, x0=x0, **extra)
@@ -1271,15 +1239,10 @@ class FridoDiffusion(_Base):
         noise: "philox", or a list with one (B, C, H, W) tensor per stage (None for a stage that does not run).
         The engine is cached per (B, latent shape, conditioning mode, T); the schedule tables and logvar are handed over on every call
         and the objective's scalars key its graphs, so a changed schedule, weight or loss type is in force at the next call."""
-        from . import autoplanes, samplers
+        from . import samplers
         from .objective import LossEngine
         unet = self.model.diffusion_model
-        if not x_start.is_cuda:
-            _no_cpu("FridoDiffusion.p_losses", x_start.device)
-        if cond is not None and not cond.is_cuda:
-            _no_cpu("FridoDiffusion.p_losses", cond.device)
-        if next(unet.parameters()).device.type != "cuda":
-            _no_cpu("FridoDiffusion.p_losses", next(unet.parameters()).device)
+        _on_gpu("FridoDiffusion.p_losses", x_start, cond, unet)
         B, C, H, W = (int(v) for v in x_start.shape)
         tl = torch.as_tensor(t).reshape(-1)
         assert tl.shape[0] == B, "t: one timestep per sample"
@@ -1301,6 +1264,15 @@ class FridoDiffusion(_Base):
                            original_elbo_weight=self.original_elbo_weight)
         return autoplanes.run(unet, go, "FridoDiffusion.p_losses")
 
+    def _noise_tape(self, noise, shape, stages):
+        """_objective's `noise` from p_losses' / forward's: "philox" as it is; else one entry per stage of the model, for the stages of
+        `stages` the given tensor or (None / "torch") a randn(shape) of its own from the host generator, in stage order, None elsewhere."""
+        if isinstance(noise, str) and noise == "philox":
+            return "philox"
+        host = noise is None or isinstance(noise, str)
+        given = {s: torch.randn(tuple(shape)) if host else noise for s in stages}
+        return [given.get(s) for s in range(self.num_resulotion)]
+
     def _loss_dict(self, row, stage):
         """p_losses' dict of one stage row (frido.py:1188-1222), values as 0-dim device tensors."""
         prefix = "train" if self.training else "val"
@@ -1320,11 +1292,7 @@ class FridoDiffusion(_Base):
         return_per_sample: also the per-sample loss_simple [B]."""
         self._objective_refuse(cond)
         stage = int(stage)
-        if isinstance(noise, str) and noise == "philox":
-            tape = "philox"
-        else:
-            n = torch.randn(tuple(x_start.shape)) if noise is None or isinstance(noise, str) else noise
-            tape = [n if s == stage else None for s in range(self.num_resulotion)]
+        tape = self._noise_tape(noise, x_start.shape, (stage,))
         assert 0 <= stage < self.num_resulotion, f"stage {stage}: the model has {self.num_resulotion}"
         rows, per = self._objective(x_start, cond, t, tape, seed, sample0, stages=(stage,))
         out = self._loss_dict(rows[stage], stage)
@@ -1348,13 +1316,7 @@ class FridoDiffusion(_Base):
                 c = self.get_learned_conditioning(c)
         S = self.num_resulotion
         assert len(self.stage_loss_ratio) == S, "Incorrect number of stage_loss_ratio."
-        if isinstance(noise, str) and noise == "philox":
-            tape = "philox"
-        elif noise is None or isinstance(noise, str):
-            tape = [torch.randn(tuple(x.shape)) for _ in range(S)]
-        else:
-            tape = [noise] * S
-        rows, _ = self._objective(x, c, t, tape, seed, sample0)
+        rows, _ = self._objective(x, c, t, self._noise_tape(noise, x.shape, range(S)), seed, sample0)
         total_loss = torch.zeros((), device=x.device)
         total_loss_dict = dict()
         for s in range(S):

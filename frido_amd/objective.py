@@ -17,6 +17,7 @@ import torch
 
 from . import _lib
 from .builder import Builder
+from .engine import lru_entry, own_stream
 from .patching import FOREIGN, PatchProg
 from .runtime import _relayout
 from .unet_plan import UNetStagePlan
@@ -77,11 +78,6 @@ class LossEngine:
         self._rng_host = (0, 0)
         self._logvar_zero = torch.zeros(self.T)
         self._logvar_host = self._logvar_zero
-
-    def _stream_obj(self):
-        if self._stream is None:
-            self._stream = torch.cuda.Stream(device=self.dev)
-        return self._stream
 
     def _set_logvar(self, logvar):
         """The device copy of the model's logvar.  A host tensor (the reference keeps it on the CPU unless it is learned) is uploaded only
@@ -146,10 +142,7 @@ class LossEngine:
         stages = tuple(range(self.num_stage)) if stages is None else tuple(int(s) for s in stages)
         assert stages and all(0 <= s < self.num_stage for s in stages), stages
         sc = (LOSS_TYPES[loss_type], float(mix_tau), float(l_simple_weight), float(original_elbo_weight))
-        stream = self._stream_obj()
-        stream.wait_stream(torch.cuda.current_stream(self.dev))
-        sp = stream.cuda_stream
-        with torch.cuda.stream(stream):
+        with own_stream(self, self.dev) as sp:
             _relayout(self.b, sp, x.contiguous().float(), self.x0, B, H * W, Cn, 0)
             self.t.copy_(torch.as_tensor(t, dtype=torch.int64).reshape(B))
             for dst, src in zip((self.sqrt_ac, self.sqrt_1mac, self.lvlb), tables):
@@ -173,17 +166,13 @@ class LossEngine:
                 self.rng[0].fill_(self._rng_host[0])                      # scalar kernel arguments: no host buffer the stream would wait for
                 self.rng[1].fill_(self._rng_host[1])
             key = ("tape" if tape is not None else "philox", stages, sc)
-            if key in self.graphs:
-                self.graphs.move_to_end(key)
-            else:
-                while len(self.graphs) >= self.GRAPHS:
-                    stream.synchronize()                                  # (rare) a graph must not go while a replay of it is queued
-                    self.graphs.popitem(last=False)
+
+            def capture():
                 prog = self.program(tape is not None, stages, sc)
-                self.graphs[key] = prog.capture(sp) if self.use_graph else prog
+                g = prog.capture(sp) if self.use_graph else prog
                 self.graph_captures += 1
-            g = self.graphs[key]
+                return g
+            # (rare) a graph must not go while a replay of it is queued: the stream is drained before one is dropped
+            g = lru_entry(self.graphs, key, self.GRAPHS, capture, before_evict=self._stream.synchronize)
             g.launch(sp) if self.use_graph else g.run(sp)
-            out = self.rows.clone(), self.per_sample.clone()
-        torch.cuda.current_stream(self.dev).wait_stream(stream)
-        return out
+            return self.rows.clone(), self.per_sample.clone()

@@ -11,7 +11,6 @@
   DecoderRuntime   — VQModelInterface.decode / decode_first_stage on the HIP engine; MSFPNVQModel's encode_quant / decode_quant /
                      reconstruct (encode program, codebook loss and decode program as one captured graph).
 """
-import contextlib
 import os
 from types import SimpleNamespace
 
@@ -20,7 +19,7 @@ import torch
 
 from . import _lib, config
 from .builder import Builder
-from .engine import Prog, current_stream_ptr, require_gpu
+from .engine import Prog, current_stream_ptr, own_stream, require_gpu
 from .patching import FOREIGN, PatchProg
 from .schedules import ancestral_table, dpm_solver_table, sampler_coef_table
 from .unet_plan import UNetStagePlan
@@ -55,15 +54,27 @@ def _relayout(builder, st, src, dst, B, HW, Cn, to_nchw, c0=0, Cuse=None, Cdst=N
           Cdst=Cuse if Cdst is None else Cdst, d0=0, to_nchw=to_nchw)
 
 
-class DenoiserRuntime:
+def module_builder(module, device, precision):
+    """The Builder over `module`'s weights on `device`, for the build of the library `precision` selects (_lib.use_planes)."""
+    planes = config.planes(precision)
+    with _lib.use_planes(planes):
+        device = require_gpu(device)
+    return Builder(device, config.nsplit(precision), _weights_of(module, device), planes=planes)
+
+
+class _Runtime:
+    """What a model's runtime starts from: its Builder (`b`) and that builder's device / nsplit / planes, the configuration, no plans."""
+
     def __init__(self, module, cfg, device, precision=None):
-        self.planes = config.planes(precision)      # (r05) which build of the library this model runs on: see _lib.use_planes
-        with _lib.use_planes(self.planes):
-            self.device = require_gpu(device)
+        self.b = module_builder(module, device, precision)
+        self.device, self.nsplit, self.planes = self.b.device, self.b.nsplit, self.b.planes
         self.cfg = cfg
-        self.nsplit = config.nsplit(precision)
-        self.b = Builder(self.device, self.nsplit, _weights_of(module, self.device), planes=self.planes)
         self.plans = {}
+
+
+class DenoiserRuntime(_Runtime):
+    def __init__(self, module, cfg, device, precision=None):
+        super().__init__(module, cfg, device, precision)
         self._replicas = {0: self.b}
 
     def builder_for(self, replica):
@@ -143,23 +154,43 @@ def ancestral_step(builder, x, eps, rows, coef, start, *, noise=None, temperatur
         return nchw(xo), nchw(p0)
 
 
-@torch.no_grad()
-def patch_unfold(builder, geo, x):
-    """x (B, C, H, W) f32 NCHW on the GPU -> its crops (B * L, C, kh, kw) NCHW (patching.PatchGeometry `geo`; crop l of sample b at
-    b * L + l): FRIDO_OP_RELAYOUT to NHWC, frido_unfold, FRIDO_OP_RELAYOUT back."""
+def _unfold_nhwc(builder, st, geo, x, crops=None):
+    """x (B, C, H, W) NCHW -> its crops [B * L][kh * kw][C] NHWC, into `crops` if given: FRIDO_OP_RELAYOUT to NHWC, frido_unfold."""
     from .patching import launch_unfold
+    B, Cn, H, W = x.shape
+    kh, kw = geo.src[2:4]
+    xs = torch.empty(B, H * W, Cn, dtype=torch.float32, device=x.device)
+    if crops is None:
+        crops = torch.empty(B * geo.L, kh * kw, Cn, dtype=torch.float32, device=x.device)
+    _relayout(builder, st, x, xs, B, H * W, Cn, 0)
+    launch_unfold(geo.unfold_desc(xs.data_ptr(), crops.data_ptr(), B, Cn), st)
+    return crops
+
+
+def _fold_nchw(builder, st, geo, crops, B, Cn):
+    """crops [B * L][kh' * kw'][C] NHWC -> their weighted, normalised recombination (B, C, H', W') NCHW: frido_fold, FRIDO_OP_RELAYOUT."""
+    from .patching import launch_fold
+    H, W = geo.out[:2]
+    fs = torch.empty(B, H * W, Cn, dtype=torch.float32, device=crops.device)
+    out = torch.empty(B, Cn, H, W, dtype=torch.float32, device=crops.device)
+    launch_fold(geo.fold_desc(crops.data_ptr(), fs.data_ptr(), B, Cn), st)
+    _relayout(builder, st, fs, out, B, H * W, Cn, 1)
+    return out
+
+
+@torch.no_grad()
+def patch_unfold(builder, geo, x, out=None):
+    """x (B, C, H, W) f32 NCHW on the GPU -> its crops (B * L, C, kh, kw) NCHW, into `out` if given (patching.PatchGeometry `geo`; crop l
+    of sample b at b * L + l): FRIDO_OP_RELAYOUT to NHWC, frido_unfold, FRIDO_OP_RELAYOUT back."""
     B, Cn, H, W = x.shape
     _, _, kh, kw, _, _ = geo.src
     assert (H, W) == geo.src[:2]
-    dev, Bc = x.device, B * geo.L
+    Bc = B * geo.L
     with _lib.use_planes(builder.planes):
-        st = current_stream_ptr(dev)
-        x = x.contiguous()
-        xs = torch.empty(B, H * W, Cn, dtype=torch.float32, device=dev)
-        cs = torch.empty(Bc, kh * kw, Cn, dtype=torch.float32, device=dev)
-        out = torch.empty(Bc, Cn, kh, kw, dtype=torch.float32, device=dev)
-        _relayout(builder, st, x, xs, B, H * W, Cn, 0)
-        launch_unfold(geo.unfold_desc(xs.data_ptr(), cs.data_ptr(), B, Cn), st)
+        st = current_stream_ptr(x.device)
+        cs = _unfold_nhwc(builder, st, geo, x.contiguous())
+        if out is None:
+            out = torch.empty(Bc, Cn, kh, kw, dtype=torch.float32, device=x.device)
         _relayout(builder, st, cs, out, Bc, kh * kw, Cn, 1)
     return out
 
@@ -167,21 +198,14 @@ def patch_unfold(builder, geo, x):
 @torch.no_grad()
 def patch_fold(builder, geo, o, B):
     """o (B * L, C, kh', kw') f32 NCHW crops -> the weighted, normalised recombination (B, C, H', W') NCHW (the fold side of `geo`)."""
-    from .patching import launch_fold
     Bc, Cn = o.shape[:2]
-    H, W, kh, kw, _, _ = geo.out
+    _, _, kh, kw, _, _ = geo.out
     assert Bc == B * geo.L and tuple(o.shape[2:]) == (kh, kw), (tuple(o.shape), B, geo.L, kh, kw)
-    dev = o.device
     with _lib.use_planes(builder.planes):
-        st = current_stream_ptr(dev)
-        o = o.contiguous().float()
-        cs = torch.empty(Bc, kh * kw, Cn, dtype=torch.float32, device=dev)
-        fs = torch.empty(B, H * W, Cn, dtype=torch.float32, device=dev)
-        out = torch.empty(B, Cn, H, W, dtype=torch.float32, device=dev)
-        _relayout(builder, st, o, cs, Bc, kh * kw, Cn, 0)
-        launch_fold(geo.fold_desc(cs.data_ptr(), fs.data_ptr(), B, Cn), st)
-        _relayout(builder, st, fs, out, B, H * W, Cn, 1)
-    return out
+        st = current_stream_ptr(o.device)
+        cs = torch.empty(Bc, kh * kw, Cn, dtype=torch.float32, device=o.device)
+        _relayout(builder, st, o.contiguous().float(), cs, Bc, kh * kw, Cn, 0)
+        return _fold_nchw(builder, st, geo, cs, B, Cn)
 
 
 def logged_at(n, log_every_t):
@@ -483,16 +507,6 @@ class SamplerEngine:
             launch_unfold(self.unfold_x, sp)
         plan.pre.run(sp)
 
-    @contextlib.contextmanager
-    def _own_stream(self):
-        """The engine's stream, ordered after the caller's on entry and before it on exit; yields its handle."""
-        if self._stream is None:
-            self._stream = torch.cuda.Stream(device=self.dev)
-        self._stream.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(self._stream):
-            yield self._stream.cuda_stream
-        torch.cuda.current_stream(self.dev).wait_stream(self._stream)
-
     def _to_nchw(self, nhwc, sp):
         out = torch.empty(self.B, nhwc.shape[-1], self.H, self.W, dtype=torch.float32, device=self.dev)
         _relayout(self.b, sp, nhwc, out, self.B, self.H * self.W, nhwc.shape[-1], 1)
@@ -566,7 +580,7 @@ class SamplerEngine:
                             corrector_kwargs=dict(corrector_kwargs or {}), model=model, cond=cond, temps=None, edit=edit,
                             n=edit.k if edit is not None else self.n_steps)
         o.row0 = self.n_steps - o.n
-        with self._own_stream() as sp:
+        with own_stream(self, self.dev) as sp:
             ctx = self._context(cond, uncond)
             self.cfg_dev.fill_(self.cfg_scale)
             if edit is not None:
@@ -791,7 +805,7 @@ class SamplerEngine:
         o = SimpleNamespace(draw=draw, seed=seed, sample0=sample0, log_every_t=log_every_t, callback=callback, img_callback=img_callback,
                             noise_dropout=float(noise_dropout), score_corrector=score_corrector, corrector_kwargs=dict(corrector_kwargs or {}),
                             model=model, cond=cond, temps=temps, collect=collect)
-        with self._own_stream() as sp:
+        with own_stream(self, self.dev) as sp:
             ctx = self._context(cond)
             self._init_x(x_T, draw, seed, sample0, sp)
             o.inter = [self._to_nchw(self.x, sp)] if collect == "img" else []
@@ -845,19 +859,37 @@ class SamplerEngine:
         self._replay(key, self._unit_steps(o, self.unit), logged, sp, before_unit=upload, after_unit=after)
 
 
-class DecoderRuntime:
+class DecoderRuntime(_Runtime):
     def __init__(self, module, vq_cfg, device, precision=None):
-        self.planes = config.planes(precision)
-        with _lib.use_planes(self.planes):
-            self.device = require_gpu(device)
-        self.cfg = vq_cfg
-        self.nsplit = config.nsplit(precision)
-        self.b = Builder(self.device, self.nsplit, _weights_of(module, self.device), planes=self.planes)
-        self.plans = {}
+        super().__init__(module, vq_cfg, device, precision)
         self.graphs = {}         # reconstruct(): (B, H, W, aux) -> the captured encode + loss + decode graph
         self.graph_captures = 0
 
     U8_MODES = {False: 0, None: 0, True: 1, "np": 1, "pil": 2}
+
+    def _per_scale(self, factors):
+        """A per-scale factor list as the tuple of floats the plan keys hold; None: all ones."""
+        return tuple(float(v) for v in (factors if factors is not None else [1.0] * len(self.cfg["embed_dim"])))
+
+    def _dec(self, B, h, w, Ct, inv_scale, forced, u8):
+        """(latent state [B][h * w][Ct], VQ decode plan) of one latent shape: the whole-latent decode and the patch-wise decode of crops of
+        that shape share it."""
+        inv = self._per_scale(inv_scale)
+        key = (B, h, w, inv, forced, u8)
+        if key not in self.plans:
+            z_state = torch.zeros(B, h * w, Ct, dtype=torch.float32, device=self.device)
+            self.plans[key] = (z_state, VQDecodePlan(self.b, self.cfg["ddconfig"], self.cfg["embed_dim"], self.cfg["n_embed"], B=B, h=h, w=w,
+                                                      z_state=z_state, inv_scale=inv, forced=forced, u8_mode=u8))
+        return self.plans[key]
+
+    def _enc(self, B, Cin, H, W, scale):
+        """(input buffer (B, Cin, H, W), pre-quant encode plan) of one image shape, shared like _dec's."""
+        sc = self._per_scale(scale)
+        key = ("enc", B, H, W, sc)
+        if key not in self.plans:
+            x_in = torch.zeros(B, Cin, H, W, dtype=torch.float32, device=self.device)
+            self.plans[key] = (x_in, VQEncodePlan(self.b, self.cfg, B=B, H=H, W=W, x_in=x_in, scale=sc))
+        return self.plans[key]
 
     @_lib.with_planes
     def decode(self, z, inv_scale=None, return_code=False, to_uint8=False, force_codes=None):
@@ -866,16 +898,9 @@ class DecoderRuntime:
         pixel bytes of :103-113 (custom_to_pil's truncating conversion), written by the LAST conv's epilogue (r04: no f32
         image, 4x less to gather / write)."""
         B, Ct, h, w = z.shape
-        embed = self.cfg["embed_dim"]
-        inv = tuple(float(v) for v in (inv_scale if inv_scale is not None else [1.0] * len(embed)))
         u8 = self.U8_MODES[to_uint8]
-        key = (B, h, w, inv, force_codes is not None, u8)
         st = current_stream_ptr(self.device)
-        if key not in self.plans:
-            z_state = torch.zeros(B, h * w, Ct, dtype=torch.float32, device=self.device)
-            self.plans[key] = (z_state, VQDecodePlan(self.b, self.cfg["ddconfig"], embed, self.cfg["n_embed"], B=B, h=h, w=w,
-                                                      z_state=z_state, inv_scale=inv, forced=force_codes is not None, u8_mode=u8))
-        z_state, plan = self.plans[key]
+        z_state, plan = self._dec(B, h, w, Ct, inv_scale, force_codes is not None, u8)
         if force_codes is not None:      # test hook: decode the given per-scale code maps instead of the argmin's
             for dst, src in zip(plan.force_idx, force_codes):
                 dst.copy_(torch.as_tensor(src, dtype=torch.int64).reshape(-1))
@@ -883,29 +908,19 @@ class DecoderRuntime:
         _relayout(self.b, st, zc, z_state, B, h * w, Ct, 0)
         plan.prog.run(st)
         if u8:
-            img = plan.out_u8.view(B, plan.H, plan.W, plan.a.out_ch).clone()
-            return (img, [i.view(B, -1) for i in plan.idx]) if return_code else img
-        out = torch.empty(B, plan.a.out_ch, plan.H, plan.W, dtype=torch.float32, device=self.device)
-        _relayout(self.b, st, plan.out_nhwc, out, B, plan.H * plan.W, plan.a.out_ch, 1)
-        if return_code:
-            return out, [i.view(B, -1) for i in plan.idx]
-        return out
+            out = plan.out_u8.view(B, plan.H, plan.W, plan.a.out_ch).clone()
+        else:
+            out = torch.empty(B, plan.a.out_ch, plan.H, plan.W, dtype=torch.float32, device=self.device)
+            _relayout(self.b, st, plan.out_nhwc, out, B, plan.H * plan.W, plan.a.out_ch, 1)
+        return (out, [i.view(B, -1) for i in plan.idx]) if return_code else out
 
     @_lib.with_planes
     def encode(self, x, scale=None):
         """x (B, 3, H, W) NCHW image -> pre-quantisation latent (B, sum(embed), H/f, W/f); `scale` (per scale) folds
         get_first_stage_encoding's multiply in."""
-        B, Cin, H, W = x.shape
-        embed = self.cfg["embed_dim"]
-        sc = tuple(float(v) for v in (scale if scale is not None else [1.0] * len(embed)))
-        key = ("enc", B, H, W, sc)
-        st = current_stream_ptr(self.device)
-        if key not in self.plans:
-            x_in = torch.zeros(B, Cin, H, W, dtype=torch.float32, device=self.device)
-            self.plans[key] = (x_in, VQEncodePlan(self.b, self.cfg, B=B, H=H, W=W, x_in=x_in, scale=sc))
-        x_in, plan = self.plans[key]
+        x_in, plan = self._enc(*x.shape, scale)
         x_in.copy_(x)            # plumbing: D2D copy into the plan's fixed input buffer
-        plan.prog.run(st)
+        plan.prog.run(current_stream_ptr(self.device))
         return plan.out.clone()
 
     # ---- the MS-VQGAN as a model of its own (MSFPNVQModel: taming/models/msvqgan.py:116-186, 266-309) ----
@@ -930,11 +945,6 @@ class DecoderRuntime:
             self.plans[key] = (q_in, VQDecodeQuantPlan(self.b, self.cfg["ddconfig"], embed, Bs=Bs, h=h, w=w, quant_src=q_in,
                                                        groups=groups, u8_mode=u8))
         return self.plans[key]
-
-    def _stream_obj(self):
-        if getattr(self, "_stream", None) is None:
-            self._stream = torch.cuda.Stream(device=self.device)
-        return self._stream
 
     @_lib.with_planes
     def encode_quant(self, x):
@@ -982,10 +992,7 @@ class DecoderRuntime:
         x_in, enc, loss = self._encq(B, Cin, H, W)
         h, w = enc.quant.shape[2:]
         _, dec = self._decq(B, h, w, self.aux_groups() if aux else None, 0, src=enc.quant)
-        stream = self._stream_obj()
-        stream.wait_stream(torch.cuda.current_stream(self.device))
-        sp = stream.cuda_stream
-        with torch.cuda.stream(stream):
+        with own_stream(self, self.device) as sp:
             x_in.copy_(x)
             key = ("rec", B, H, W, bool(aux), bool(use_graph))
             if key not in self.graphs:
@@ -996,9 +1003,7 @@ class DecoderRuntime:
                 self.graph_captures += 1
             g = self.graphs[key]
             g.launch(sp) if use_graph else g.run(sp)
-            out = dec.out.clone(), enc.quant.clone(), loss.total.clone(), [i.clone() for i in enc.idx]
-        torch.cuda.current_stream(self.device).wait_stream(stream)
-        return out
+            return dec.out.clone(), enc.quant.clone(), loss.total.clone(), [i.clone() for i in enc.idx]
 
     # ---- patch-wise mode (FridoDiffusion.split_input_params with patch_distributed_vq, frido.py:840-877, 963-993) ----
     @_lib.with_planes
@@ -1006,71 +1011,36 @@ class DecoderRuntime:
         """z (B, Ctot, h, w) NCHW latent -> image (B, 3, h * vqf, w * vqf): the latent's crops (patching.PatchGeometry `geo`, DECODE mode) are
         decoded as ONE batch of B * L by the decode plan (f32 NHWC crops out of its last conv) and folded at image resolution; with
         to_uint8 the fold kernel writes the (B, H, W, 3) uint8 image through the last conv's two conversions."""
-        from .patching import launch_fold, launch_unfold
-        B, Ct, h, w = z.shape
+        from .patching import launch_fold
+        B, Ct = z.shape[:2]
         _, _, kh, kw, _, _ = geo.src
         H, W, kho, kwo, _, _ = geo.out
-        embed = self.cfg["embed_dim"]
-        inv = tuple(float(v) for v in (inv_scale if inv_scale is not None else [1.0] * len(embed)))
         u8 = self.U8_MODES[to_uint8]
-        Bc = B * geo.L
-        key = (Bc, kh, kw, inv, False, 0)
         st = current_stream_ptr(self.device)
-        if key not in self.plans:
-            z_state = torch.zeros(Bc, kh * kw, Ct, dtype=torch.float32, device=self.device)
-            self.plans[key] = (z_state, VQDecodePlan(self.b, self.cfg["ddconfig"], embed, self.cfg["n_embed"], B=Bc, h=kh, w=kw,
-                                                      z_state=z_state, inv_scale=inv, forced=False, u8_mode=0))
-        z_state, plan = self.plans[key]
+        z_state, plan = self._dec(B * geo.L, kh, kw, Ct, inv_scale, False, 0)
         if (plan.H, plan.W) != (kho, kwo):
             raise ValueError(f"split_input_params['vqf'] = {kho // kh} does not match the first stage, which decodes {kh} x {kw} latents to "
                              f"{plan.H} x {plan.W} images")
         Co = plan.a.out_ch
-        zc = z.contiguous().float()
-        zs = torch.empty(B, h * w, Ct, dtype=torch.float32, device=self.device)
-        _relayout(self.b, st, zc, zs, B, h * w, Ct, 0)
-        launch_unfold(geo.unfold_desc(zs.data_ptr(), z_state.data_ptr(), B, Ct), st)
+        _unfold_nhwc(self.b, st, geo, z.contiguous().float(), crops=z_state)
         plan.prog.run(st)
         if u8:
             img = torch.empty(B, H, W, Co, dtype=torch.uint8, device=self.device)
             launch_fold(geo.fold_desc(plan.out_nhwc.data_ptr(), None, B, Co, out_u8=img.data_ptr(), u8_mode=u8), st)
             return img
-        fs = torch.empty(B, H * W, Co, dtype=torch.float32, device=self.device)
-        launch_fold(geo.fold_desc(plan.out_nhwc.data_ptr(), fs.data_ptr(), B, Co), st)
-        out = torch.empty(B, Co, H, W, dtype=torch.float32, device=self.device)
-        _relayout(self.b, st, fs, out, B, H * W, Co, 1)
-        return out
+        return _fold_nchw(self.b, st, geo, plan.out_nhwc, B, Co)
 
     @_lib.with_planes
     def encode_patches(self, x, geo):
         """x (B, 3, H, W) NCHW image -> pre-quantisation latent (B, sum(embed), H / vqf, W / vqf): image crops (`geo`, ENCODE mode) encoded
         as one batch, folded at latent resolution."""
-        from .patching import launch_fold, launch_unfold
-        B, Cin, H, W = x.shape
+        B, Cin = x.shape[:2]
         _, _, kh, kw, _, _ = geo.src
-        Ho, Wo, kho, kwo, _, _ = geo.out
-        embed = self.cfg["embed_dim"]
-        Bc = B * geo.L
-        key = ("enc", Bc, kh, kw, tuple([1.0] * len(embed)))
-        st = current_stream_ptr(self.device)
-        if key not in self.plans:
-            x_in = torch.zeros(Bc, Cin, kh, kw, dtype=torch.float32, device=self.device)
-            self.plans[key] = (x_in, VQEncodePlan(self.b, self.cfg, B=Bc, H=kh, W=kw, x_in=x_in, scale=key[4]))
-        x_in, plan = self.plans[key]
-        Ce = plan.out.shape[1]
+        _, _, kho, kwo, _, _ = geo.out
+        x_in, plan = self._enc(B * geo.L, Cin, kh, kw, None)
         if tuple(plan.out.shape[2:]) != (kho, kwo):
             raise ValueError(f"split_input_params['vqf'] = {kh // kho} does not match the first stage, which encodes {kh} x {kw} images to "
                              f"{tuple(plan.out.shape[2:])} latents")
-        xc = x.contiguous().float()
-        xs = torch.empty(B, H * W, Cin, dtype=torch.float32, device=self.device)
-        cs = torch.empty(Bc, kh * kw, Cin, dtype=torch.float32, device=self.device)
-        _relayout(self.b, st, xc, xs, B, H * W, Cin, 0)
-        launch_unfold(geo.unfold_desc(xs.data_ptr(), cs.data_ptr(), B, Cin), st)
-        _relayout(self.b, st, cs, x_in, Bc, kh * kw, Cin, 1)
-        plan.prog.run(st)
-        os_ = torch.empty(Bc, kho * kwo, Ce, dtype=torch.float32, device=self.device)
-        fs = torch.empty(B, Ho * Wo, Ce, dtype=torch.float32, device=self.device)
-        out = torch.empty(B, Ce, Ho, Wo, dtype=torch.float32, device=self.device)
-        _relayout(self.b, st, plan.out, os_, Bc, kho * kwo, Ce, 0)
-        launch_fold(geo.fold_desc(os_.data_ptr(), fs.data_ptr(), B, Ce), st)
-        _relayout(self.b, st, fs, out, B, Ho * Wo, Ce, 1)
-        return out
+        patch_unfold(self.b, geo, x.contiguous().float(), out=x_in)
+        plan.prog.run(current_stream_ptr(self.device))
+        return patch_fold(self.b, geo, plan.out, B)

@@ -17,6 +17,7 @@ ENGINE_CACHE_SIZE = 4      # compiled SamplerEngines kept per denoiser (each own
 
 from . import schedules
 from ._lib import FridoHipError
+from .engine import lru_entry
 
 
 def check_conditioning(unet, conditioning, batch_size, name="conditioning"):
@@ -46,16 +47,10 @@ def check_conditioning(unet, conditioning, batch_size, name="conditioning"):
 
 
 def cached_engine(rt, key, make):
-    """The denoiser runtime's least-recently-used cache of SamplerEngines, shared by every sampler kind: `make()` builds a missing one."""
-    cache = rt.__dict__.setdefault("_sampler_engines", collections.OrderedDict())
-    if key in cache:
-        cache.move_to_end(key)
-    else:
-        while len(cache) >= ENGINE_CACHE_SIZE:      # least-recently-used engine goes; it owns its plans' persistent buffers
-            # (Builder.persist_scope) and graphs, so its HBM is released with it -- the activation pool is shared and reused
-            cache.popitem(last=False)
-        cache[key] = make()
-    return cache[key]
+    """The denoiser runtime's least-recently-used cache of SamplerEngines, shared by every sampler kind: `make()` builds a missing one.
+    An evicted engine owns its plans' persistent buffers (Builder.persist_scope) and graphs, so its HBM is released with it -- the
+    activation pool is shared and reused."""
+    return lru_entry(rt.__dict__.setdefault("_sampler_engines", collections.OrderedDict()), key, ENGINE_CACHE_SIZE, make)
 
 
 def edit_steps(S, t_start=None, strength=None):
