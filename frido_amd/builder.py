@@ -4,7 +4,6 @@ descriptors, owning the packed-weight cache and the activation pool.  The U-Net 
 """
 import contextlib
 import ctypes as C_
-import os
 
 import torch
 
@@ -13,30 +12,14 @@ from .arch import MH_HEAD_DIMS, check_attention_heads      # noqa: F401  (re-exp
 from .engine import (Operand, POperand, F32, Alias, Pool, Prog, pack_matrix, pack_conv_weight, rup)
 
 ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2
-UP2_PHASES = os.environ.get("FRIDO_UP2_PHASES", "1") != "0"       # Upsample convs as four 2x2 phase convolutions
-GN_FUSED = os.environ.get("FRIDO_GN_FUSED", "1") != "0"          # one-launch GroupNorm (norm.hip gn_fused_kernel)
-GN_CONV_TINY = os.environ.get("FRIDO_GN_CONV_TINY", "1") != "0"     # r06: the eps head (GroupNorm + SiLU + conv3x3 to 3 / 4 channels) as ONE f32 VALU launch (tile 40)
-GN_FUSED_MAX_HW = int(os.environ.get("FRIDO_GN_FUSED_MAX_HW", "256"))   # larger planes: gn_stats + gn_apply are faster
-# r04: a split-K GEMM whose output goes straight into a one-launch GroupNorm leaves its reduction to that launch (no splitk_reduce)
-SK_DEFER = os.environ.get("FRIDO_SK_DEFER", "1") != "0"
-GN_EPI_STATS = os.environ.get("FRIDO_GN_EPI_STATS", "1") != "0"   # GroupNorm partial sums from the producing GEMM's epilogue (bf16x3 f32 stream)
-LN_IN_ATTN = os.environ.get("FRIDO_LN_IN_ATTN", "1") != "0"       # norm2 / norm3 of a transformer block from the attention kernel's epilogue (A/B switch)
-ATTN_FLASH = os.environ.get("FRIDO_ATTN_FLASH", "1") != "0"       # flash-style kernel for long key sequences (flash.hip)
-# below this many keys the score matrix is small and the batched GEMM -> softmax -> GEMM chain fills the chip better than
-# one workgroup per 64 queries (measured at B = 16: 256 keys x d = 576: 37 us vs 49 us; 1024 keys x d = 384: 102 vs 82 us)
-ATTN_FLASH_MIN_KEYS = int(os.environ.get("FRIDO_ATTN_FLASH_MIN_KEYS", "512"))
-# SHORT key sequences (cross-attention: 26 / 92 / 1 tokens) on planes with at least this many queries per sample also take the
-# flash kernel (one 32-key tile, no cross-wave score exchange) instead of the 16-query short-key kernel; 0 = never
-ATTN_FLASH_SHORT_NQ = int(os.environ.get("FRIDO_ATTN_FLASH_SHORT_NQ", "0"))
-# GroupNorm-apply fused into the 3x3 conv that consumes it (csrc/convgn.inc, two-plane mode, 64^2 / 32^2 planes): "1" = where the
-# launch fills the chip (>= 224 workgroups), "0" = never (gn_apply + ring conv: the r03 path), "force" = wherever the kernel applies
-GN_CONV = os.environ.get("FRIDO_GN_CONV", "1")
-# fused kernel with K split over slices on the 16 x 16 planes (48 tiles): built, tested, measured -- a tie per launch (100 us vs 100.5 us for
-# gn_fused + the split-K ring conv) and -2.3 % end to end (profiles/r04_gnconv_splitk_ab.txt: few chunks per slice leave the prologue's
-# un-overlapped staging and the 196-KB partial-sum epilogue uncovered), so it stays OFF; the C ABI keeps the option (FridoGemm.splitk on tiles 20 / 21)
-GN_CONV_SPLITK = os.environ.get("FRIDO_GN_CONV_SPLITK", "0") != "0"
-ATTN_SKIP_DEAD_STREAM = os.environ.get("FRIDO_ATTN_SKIP_DEAD_STREAM", "1") != "0"      # r05: cross-attention does not store f32 rows nobody reads (A/B switch)
-GN_CONV_PREFER = int(os.environ.get("FRIDO_GN_CONV_PREFER", "256"))      # A/B: which tile height is tried first where both fill the chip
+# Plan-time thresholds.  None of them is read from the environment: the tests set or name them (monkeypatch) to reach both sides.
+GN_FUSED_MAX_HW = 256   # test knob: one-launch GroupNorm (norm.hip gn_fused_kernel) up to this plane size; larger planes: gn_stats + gn_apply are faster
+# test knob (r04): a split-K GEMM whose output goes straight into a one-launch GroupNorm leaves its reduction to that launch (no splitk_reduce)
+SK_DEFER = True
+# test knob: from this many keys on, the flash-style kernel (flash.hip).  Below it the score matrix is small and the batched
+# GEMM -> softmax -> GEMM chain fills the chip better than one workgroup per 64 queries (measured at B = 16: 256 keys x d = 576:
+# 37 us vs 49 us; 1024 keys x d = 384: 102 vs 82 us)
+ATTN_FLASH_MIN_KEYS = 512
 
 
 class Builder:
@@ -275,7 +258,7 @@ class Builder:
     def upsample_conv(self, a, B, Hs, Ws, wname):
         """Upsample block: nearest x2 + conv3x3.  Four 2x2 phase convolutions when the plane allows it, else the 9-tap
         conv with the up-sampling folded into its addressing."""
-        if UP2_PHASES and Hs & (Hs - 1) == 0 and Ws & (Ws - 1) == 0:
+        if Hs & (Hs - 1) == 0 and Ws & (Ws - 1) == 0:
             return self.conv_up2(a, B, Hs, Ws, wname)
         return self.conv(a, B, Hs, Ws, wname, up=1)
 
@@ -367,7 +350,7 @@ class Builder:
     def _parts_for(self, res, M, N, *, act=0, rowvec=None, residual=None, up2=False):
         """Partial-sum buffer for the GEMM about to write the f32 stream activation `res` (FridoGemm.gn_part), or None when the
         launch does not take the store-from-registers f32 epilogue (mirror of the library's check in frido_gemm)."""
-        if not (GN_EPI_STATS and self.nsplit == 2 and not getattr(res, "bf16", True) and act == 0 and not up2 and N % 8 == 0 and M % 32 == 0):
+        if not (self.nsplit == 2 and not getattr(res, "bf16", True) and act == 0 and not up2 and N % 8 == 0 and M % 32 == 0):
             return None
         if rowvec is not None and (rowvec.get("rows_per_vec") or 0) < (1 << 29):
             return None
@@ -383,30 +366,23 @@ class Builder:
             res.gn_part = None
 
     def gn_conv_tile(self, x1, x2, B, H, W, co, raw=None):
-        """(tile, splitk) of the fused GroupNorm + 3x3 conv kernel for this plane -- FridoGemm tile 20 (256-row tiles) or 21 (128-row),
-        K split over `splitk` slices where the tiles alone would leave the chip idle (16 x 16 planes) -- or (0, 1) when the launch
-        does not qualify / cannot fill the chip (the caller then emits groupnorm() + conv())."""
-        if GN_CONV == "0" or self.nsplit != 2 or self.device.type != "cuda":
-            return 0, 1
+        """Tile of the fused GroupNorm + 3x3 conv kernel (csrc/convgn.hip, two-plane mode) for this plane -- FridoGemm tile 20 (256-row
+        tiles, tried first) or 21 (128-row) -- or 0 when the launch does not qualify or cannot fill the chip (< 224 workgroups: the
+        caller then emits groupnorm() + conv()).  The kernel's split-K form (FridoGemm.splitk on tiles 20 / 21, gn_conv(splitk=)) is
+        never planned: -2.3 % end to end on the 16 x 16 planes (profiles/r04_gnconv_splitk_ab.txt)."""
+        if self.nsplit != 2 or self.device.type != "cuda":
+            return 0
         tensors = [x1] + ([x2] if x2 is not None else []) + [r for r in (raw or ()) if r is not None]
         if any(getattr(t, "bf16", False) or t.C % 32 for t in tensors):
-            return 0, 1
+            return 0
         C = x1.C + (x2.C if x2 is not None else 0)
         if C > 960 or C % 32 or co % 192 or W not in (16, 32, 64) or (H * W) % 128:
-            return 0, 1
+            return 0
         M = B * H * W
-        order = ((20, 256, 396), (21, 128, 204)) if GN_CONV_PREFER == 256 else ((21, 128, 204), (20, 256, 396))
-        fits = [(tile, bm) for tile, bm, slots in order if not ((H * W) % bm or bm % W or (bm // W + 2) * (W + 2) > slots)]
-        for tile, bm in fits:
-            if GN_CONV == "force" or (M // bm) * (co // 192) >= 224:
-                return tile, 1
-        if GN_CONV_SPLITK:
-            for tile, bm in fits:       # split-K: ~256 workgroups, every slice at least two 32-channel chunks (18 k-steps)
-                tiles = (M // bm) * (co // 192)
-                sk = min(-(-256 // tiles), (C // 32) // 2, 8)
-                if sk >= 2 and tiles * sk >= 192:
-                    return tile, sk
-        return 0, 1
+        for tile, bm, slots in ((20, 256, 396), (21, 128, 204)):
+            if not ((H * W) % bm or bm % W or (bm // W + 2) * (W + 2) > slots) and (M // bm) * (co // 192) >= 224:
+                return tile
+        return 0
 
     def gn_conv(self, tile, x1, x2, B, H, W, norm_w, eps, conv_w, *, gamma=None, beta=None, act=ACT_SILU, rowvec=None, residual=None,
                 skip=None, splitk=1):
@@ -453,7 +429,7 @@ class Builder:
 
     def gn_conv_tiny_ok(self, x, B, H, W, co):
         """The fused GroupNorm + SiLU + 3x3 conv with a TINY output width (FridoGemm tile 40: the denoiser's eps head) applies."""
-        return (GN_CONV_TINY and self.nsplit == 2 and self.device.type == "cuda" and not getattr(x, "bf16", False) and co in (3, 4)
+        return (self.nsplit == 2 and self.device.type == "cuda" and not getattr(x, "bf16", False) and co in (3, 4)
                 and x.C % 32 == 0 and x.C <= 960 and W in (16, 32, 64) and (H * W) % 256 == 0 and (256 // W + 2) * (W + 2) <= 396)
 
     def gn_conv_tiny(self, x, B, H, W, norm_w, eps, conv_w, out, act=ACT_SILU):
@@ -546,7 +522,7 @@ class Builder:
                   gb_bf16=int(getattr(gamma, "bf16", False)) if gamma is not None else 0)
         # one launch (statistics + apply from registers) wherever a (sample, group-chunk) slice fits a workgroup
         _, probe = _lib.make_op("FRIDO_OP_GN_FUSED", **kw)
-        if GN_FUSED and HW <= GN_FUSED_MAX_HW and _lib.lib().frido_gn_fused_chunk(C_.byref(probe), None) > 0:
+        if HW <= GN_FUSED_MAX_HW and _lib.lib().frido_gn_fused_chunk(C_.byref(probe), None) > 0:
             kw.update(self._deferred_splitk(x1, B * HW, x1_dead))
             self.prog.emit("FRIDO_OP_GN_FUSED", **kw)
             part = None
@@ -612,10 +588,8 @@ class Builder:
         Np = rup(Nk, 32)
         aligned = ldq % 8 == 0 and ldk % 8 == 0 and q_off % 8 == 0 and k_off % 8 == 0
         small = Nk <= 128 and Nq % 16 == 0 and d % 32 == 0 and aligned
-        flash_ok = ATTN_FLASH and aligned and _lib.lib().frido_attn_flash_supported(d)
-        short_flash = small and flash_ok and ATTN_FLASH_SHORT_NQ > 0 and Nq >= ATTN_FLASH_SHORT_NQ
-        small = small and not short_flash
-        flash = not small and flash_ok and (Nk >= ATTN_FLASH_MIN_KEYS or Nk > 4096 or short_flash)
+        flash = (not small and aligned and (Nk >= ATTN_FLASH_MIN_KEYS or Nk > 4096)
+                 and _lib.lib().frido_attn_flash_supported(d))
         if small or flash:
             # one launch, scores stay on chip: the short-key kernel (cross-attention, 8x8 planes) or the flash-style kernel
             kind = "FRIDO_OP_ATTN_SMALL" if small else "FRIDO_OP_ATTN_FLASH"
@@ -624,7 +598,7 @@ class Builder:
             if stream:
                 res = self.f32(B * Nq, d)
                 assert residual is None or getattr(residual, "bf16", False) == res.bf16
-                if ln is not None and LN_IN_ATTN and not res.bf16 and self.nsplit == 2 and (
+                if ln is not None and not res.bf16 and self.nsplit == 2 and (
                         (flash and self._flash_ln_ok(d)) or (small and B * (Nq // 16) >= 256)):
                     n = self.op(B * Nq, d)
                     kw.update(ln_op=n.ptr, ln_lo=n.lo, ld_ln=d, ln_w=self.bias(ln[0] + ".weight"), ln_b=self.bias(ln[0] + ".bias"),
@@ -635,7 +609,7 @@ class Builder:
                     o = self.op(B * Nq, d)
                     kw.update(out_op=o.ptr, out_lo=o.lo, ldo=d)
                     res.op_copy = o
-                if (stream_dead and ATTN_SKIP_DEAD_STREAM and small and getattr(res, "op_copy", None) is not None
+                if (stream_dead and small and getattr(res, "op_copy", None) is not None
                         and getattr(res, "ln_copy", None) is not None):
                     kw["skip_act_store"] = 1
                     res.stream_skipped = True

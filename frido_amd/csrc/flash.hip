@@ -23,7 +23,6 @@
 //   * bf16x3 mode (NS = 2): Q, K, V^T and P carry hi + lo bf16 planes, products are hi*hi + hi*lo + lo*hi in f32.
 #include "common.h"
 #include <atomic>
-#include <cstdlib>
 
 namespace {
 
@@ -785,27 +784,20 @@ int flash_launch(const FridoAttnSmall& d, hipStream_t s) {
     return frido_check_launch("attn_flash");
 }
 
-bool flash_dsplit_on() {
-    static const bool on = !(getenv("FRIDO_FLASH_DSPLIT") && atoi(getenv("FRIDO_FLASH_DSPLIT")) == 0);
-    return on;
-}
-
 template <int D>
 int flash_dispatch(const FridoAttnSmall& d, hipStream_t s) {
     if (d.nsplit == 2) {
         // (r05) two-plane mode: the d-split 8-wave form (two waves per SIMD) for 256 <= d <= 512 (d = 576 would need exactly the 160 KiB
-        // of a CU and 8 B of scratch: measured SLOWER than the GEMM chain on the 16 x 16 plane it would serve, 43.6 vs 36.4 us, and not kept);
-        // FRIDO_FLASH_DSPLIT=0 keeps r04's 4-wave form (A/B switch)
-        if constexpr (D >= 256 && D <= 512) {
-            if (flash_dsplit_on()) return flash_ds_launch<D>(d, s);
-        }
-        return flash_launch<D, 2, 4, (D >= 512 ? 2 : 1)>(d, s);   // hi + lo planes of Q and P: one wave per SIMD
+        // of a CU and 8 B of scratch: measured SLOWER than the GEMM chain on the 16 x 16 plane it would serve, 43.6 vs 36.4 us, and not kept)
+        if constexpr (D >= 256 && D <= 512)
+            return flash_ds_launch<D>(d, s);
+        else
+            return flash_launch<D, 2, 4, (D >= 512 ? 2 : 1)>(d, s);   // d = 128 / 576: hi + lo planes of Q and P, one wave per SIMD
     }
     // 8 waves (128 queries) per workgroup halve the L2 -> LDS bytes per FLOP; 4 waves when that would leave CUs idle or the
     // accumulators do not fit 256 registers
     if constexpr (D <= 384) {
-        static const int min_wgs = getenv("FRIDO_FLASH_NW8_MIN_WGS") ? atoi(getenv("FRIDO_FLASH_NW8_MIN_WGS")) : 200;
-        if ((int64_t)d.B * ((d.Nq + 127) / 128) >= min_wgs) return flash_launch<D, 1, 8, 1>(d, s);
+        if ((int64_t)d.B * ((d.Nq + 127) / 128) >= 200) return flash_launch<D, 1, 8, 1>(d, s);
     }
     return flash_launch<D, 1, 4, 1>(d, s);
 }
@@ -814,7 +806,7 @@ int flash_dispatch(const FridoAttnSmall& d, hipStream_t s) {
 
 extern "C" int frido_attn_flash_supported(int32_t dd) { return dd == 128 || dd == 256 || dd == 384 || dd == 512 || dd == 576; }
 // head widths whose two-plane launch can produce the LayerNorm of its stream rows (FridoAttnSmall.ln_op): the workgroup owns whole rows
-extern "C" int frido_attn_flash_ln_supported(int32_t dd) { return dd == 256 || dd == 384 || (flash_dsplit_on() && dd == 512); }
+extern "C" int frido_attn_flash_ln_supported(int32_t dd) { return dd == 256 || dd == 384 || dd == 512; }
 
 extern "C" int frido_attn_flash(const FridoAttnSmall* d, frido_stream_t s) {
     FRIDO_REQUIRE(d && d->Q && d->K && d->VT && (d->out_op || d->out_act), "null pointer");

@@ -35,7 +35,7 @@ int frido_convgn_init();
 // start late, so that from then on one slot's prologue / epilogue runs under the other slot's k-loop.  The delay in QUARTER microseconds
 // comes from FridoGemm.flags bits 8..15 (0 = none), the smallest grid it applies to from bits 16..23 in units of 64 workgroups
 // (0 = 768 workgroups), which workgroups wait from bits 24..25.
-// Python: FRIDO_STAGGER_US (a float) / FRIDO_STAGGER_MIN_WG / FRIDO_STAGGER_MODE (engine.py).
+// Python: FRIDO_STAGGER_US (a float) / FRIDO_STAGGER_MIN_WG (engine.py); bits 24..25 through FRIDO_GEMM_FLAGS only.
 // (The one-workgroup-per-CU form of the same: igemm_shared.h stagger_one_per_cu)
 // (r06) -DIG_PROF=1 (tools/igemm_prof.py; never in the shipped build): every wave of the two-plane virtual-step loop sums the shader cycles
 // (s_memtime) it spends, per k-tile,  [0] waiting for the next stage's DMA in front of the barrier, [1] inside the barrier, [2] in the rest of

@@ -4,7 +4,6 @@
 // Reductions use wave64 shuffles; cross-wave / cross-workgroup combination is in a fixed order
 // (no float atomics) so results are bit-reproducible run to run.
 #include "common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -947,22 +946,8 @@ extern "C" int frido_gn_fused_chunk(const FridoGnApply* d, int* nthreads) {
     const int C = d->C1 + d->C2;
     if (C % d->groups) return 0;
     int nt8 = 0, nt4 = 0;
-    int Cc8 = 0;      // (a lane's vector never straddles the two tensors of a virtual concat: C1 % 8 == 0)
-    {
-        const int cpg = C / d->groups;
-        int G = 1;
-        while (G <= 4 && (G * cpg) % 8) ++G;
-        if (G <= 4 && d->groups % G == 0) {
-            const int Cc = G * cpg, vpp = Cc / 8;
-            for (int nt = 256; nt <= (f32_form ? 1024 : 256); nt *= 2) {
-                if (vpp > nt) continue;
-                const int ppi = nt / vpp;
-                if ((d->HW + ppi - 1) / ppi <= (f32_form ? (nt == 1024 ? 3 : 4) : GNF_MAXV)) { nt8 = nt; Cc8 = Cc; break; }
-            }
-        }
-    }
-    static const bool v4_on = !(getenv("FRIDO_GN_FUSED_V4") && atoi(getenv("FRIDO_GN_FUSED_V4")) == 0);      // A/B switch
-    if (f32_form && v4_on) {
+    const int Cc8 = gn_fused_pick(d, 8, f32_form, &nt8);      // (a lane's vector never straddles the two tensors of a virtual concat: C1 % 8 == 0)
+    if (f32_form) {
         const int Cc4 = gn_fused_pick(d, 4, true, &nt4);
         // the 4-channel form where it at least doubles a grid that does not fill the chip (256 CUs)
         if (Cc4 > 0 && (Cc4 & 7) && (Cc8 == 0 || ((C / Cc8) * d->B < 256 && Cc4 * 2 <= Cc8))) {
@@ -988,8 +973,7 @@ extern "C" int frido_gn_fused(const FridoGnApply* d, frido_stream_t s) {
     // pixel and has all its slices' loads in flight at once (the 256-thread form walked 4 vectors x sk_n slices in 4 dependent rounds;
     // measured r04: -2 us per launch).  The statistics' wave-partial order differs from the plain launch's: deferred and undeferred
     // reductions agree to fp32 rounding (<= 1e-6 relative on the normalised output), no longer bit for bit.
-    static const bool sk1024 = !(getenv("FRIDO_GN_FUSED_SK1024") && atoi(getenv("FRIDO_GN_FUSED_SK1024")) == 0);      // A/B switch
-    if (sk1024 && d->sk_ws && !d->x_bf16 && nt < 1024 && Cc / vw <= 1024) nt = 1024;
+    if (d->sk_ws && !d->x_bf16 && nt < 1024 && Cc / vw <= 1024) nt = 1024;
     const dim3 grid(C / Cc, d->B);
     hipStream_t st = (hipStream_t)s;
     if (d->x_bf16) hipLaunchKernelGGL(gn_fused_kernel<256>, grid, dim3(256), 0, st, *d, Cc);

@@ -96,8 +96,8 @@ Side* side_of(hipStream_t main) {
     return sd;
 }
 
-int run_sync(const FridoSync& d, hipStream_t main, bool serial) {
-    if (serial || d.from == d.to) return FRIDO_OK;       // everything on one stream: already ordered
+int run_sync(const FridoSync& d, hipStream_t main) {
+    if (d.from == d.to) return FRIDO_OK;       // everything on one stream: already ordered
     Side* sd = side_of(main);
     if (!sd) {
         frido_set_error("frido_run: cannot create the side stream");
@@ -113,14 +113,14 @@ int run_sync(const FridoSync& d, hipStream_t main, bool serial) {
     return FRIDO_OK;
 }
 
-int run_prog(const FridoOp* ops, int32_t n, frido_stream_t s, bool serial) {
+int run_prog(const FridoOp* ops, int32_t n, frido_stream_t s) {
     for (int32_t i = 0; i < n; ++i) {
         int rc;
         if (ops[i].kind == FRIDO_OP_SYNC) {
-            rc = run_sync(ops[i].u.sync, (hipStream_t)s, serial);
+            rc = run_sync(ops[i].u.sync, (hipStream_t)s);
         } else {
             frido_stream_t st = s;
-            if (ops[i].stream == 1 && !serial) {
+            if (ops[i].stream == 1) {
                 Side* sd = side_of((hipStream_t)s);
                 if (!sd) {
                     frido_set_error("frido_run: cannot create the side stream");
@@ -147,8 +147,7 @@ extern "C" int frido_run(const FridoOp* ops, int32_t n, frido_stream_t s) {
         frido_set_error("frido_run: bad arguments");
         return FRIDO_EINVAL;
     }
-    static const bool serial = getenv("FRIDO_SERIAL") && atoi(getenv("FRIDO_SERIAL")) != 0;     // A/B: ignore the side stream
-    return run_prog(ops, n, s, serial);
+    return run_prog(ops, n, s);
 }
 
 extern "C" int frido_run_timed(const FridoOp* ops, int32_t n, frido_stream_t s, float* ms) {

@@ -13,7 +13,9 @@ from . import _lib
 
 import contextlib
 import os
-SIDE_STREAM = os.environ.get("FRIDO_SIDE_STREAM", "0") != "0"   # independent projections of an attention block on a side stream: measured -2.9 % (the fork / join nodes cost more than the overlap buys), off by default
+# test knob: Prog.sync / Prog.side emit for the executor's side stream (FRIDO_OP_SYNC, FridoOp.stream).  No plan uses them: independent projections of an
+# attention block on a side stream measured -2.9 % (the fork / join nodes cost more than the overlap buys)
+SIDE_STREAM = False
 GEMM_FLAGS = int(os.environ.get("FRIDO_GEMM_FLAGS", "0"))     # FridoGemm.flags A/B switches (include/frido_hip.h)
 # Staggered start (r05 experiment, SHIPPED in r06: the kernels always honour FridoGemm.flags bits 8..25; results are
 # unchanged bit for bit): start delay in microseconds of the second resident slot (dispatch ids 256 .. 511) of a multi-round two-per-CU
@@ -21,16 +23,8 @@ GEMM_FLAGS = int(os.environ.get("FRIDO_GEMM_FLAGS", "0"))     # FridoGemm.flags 
 # other's k-loop from then on.  12 us: + 2.1 % end to end (interleaved, profiles/r06_stagger_*.txt; 8 us on the r05 boxes: + 2.0 ... 2.5 %).
 STAGGER_US = float(os.environ.get("FRIDO_STAGGER_US", "12"))         # quarter-microsecond resolution, at most 63.75; 0 = off
 STAGGER_MIN_WG = int(os.environ.get("FRIDO_STAGGER_MIN_WG", "0"))
-STAGGER_MODE = int(os.environ.get("FRIDO_STAGGER_MODE", "0"))        # 0: dispatch ids 256..511 wait; 1: every other workgroup of an XCD (control)
-STAGGER_8W = int(os.environ.get("FRIDO_STAGGER_8W", "0"))            # 1: the one-workgroup-per-CU kernels too (odd XCDs start late; igemm_shared.h)
-GEMM_FLAGS |= (((int(round(STAGGER_US * 4)) & 255) << 8) | (((STAGGER_MIN_WG // 64) & 255) << 16) | ((STAGGER_MODE & 3) << 24)
-               | ((STAGGER_8W & 1) << 26))
-# (r06) column-panel tile order of the ring GEMM kernel (igemm.hip; FridoGemm.flags bit 27): keeps a launch's weight panel L2-resident per XCD.
-# Built on a PMC finding (the GEGLU projection fetches 162 MB per launch for 30 MB of operands, L2 hit rate 81 %: profiles/r06_pmc_l2_by_instance_*.json);
-# measured: -5 % per GEGLU launch in the back-to-back microbenchmark, +0.06 % end to end (three interleaved pairs, profiles/r06_panels_*.txt) -- the L2
-# misses are not what paces these k-loops.  OFF by default: the r05 tile order stays the validated one.
-GEMM_PANELS = os.environ.get("FRIDO_GEMM_PANELS", "0") != "0"
-GEMM_FLAGS |= (1 << 27) if GEMM_PANELS else 0
+# (bits 24..27 -- the stagger control forms and the column-panel tile order, all measured and left off -- are reachable through FRIDO_GEMM_FLAGS only)
+GEMM_FLAGS |= ((int(round(STAGGER_US * 4)) & 255) << 8) | (((STAGGER_MIN_WG // 64) & 255) << 16)
 BF16X3 = 2   # nsplit: hi + residual plane, 3 MFMAs per product (≈ fp32 accuracy)
 BF16 = 1     # nsplit: plain bf16 operands
 
@@ -309,9 +303,7 @@ class Prog:
                 # in the environment overrides every pinned delay
                 st.flags = (st.flags & ~0xFF00) | ((int(choice[2]) & 255) << 8)
             if st.splitk > 1:
-                st.sk_mode = tune.SK_MODE
-                if not st.sk_mode:
-                    st.gn_part = None   # the split-K reduction kernel does not produce them (the consumer falls back to gn_stats)
+                st.gn_part = None   # the split-K reduction kernel does not produce them (the consumer falls back to gn_stats)
                 # ops of the executor's side stream run CONCURRENTLY with main-stream ops: they get their own workspace
                 st.ws = tune.workspace_for(st, self.device, self.ws_tag + (":s1" if self._sid else ""))
         self.flops += 2 * M * N * (K + K2) * batch * (3 if self.nsplit == 2 else 1)

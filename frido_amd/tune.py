@@ -18,33 +18,19 @@ TILES8W = (7, 8)                    # 8-wave 256-row tiles (bf16 mode)
 _cache = {}
 _scratch = {}
 ENABLED = os.environ.get("FRIDO_TUNE", "1") != "0"
-K64_ALL = os.environ.get("FRIDO_TUNE_K64_ALL", "1") != "0"           # try the BK = 64 tiles on every shape, not only small M
-BIG_SPLITK = os.environ.get("FRIDO_TUNE_BIG_SPLITK", "1") != "0"      # also try the 8-wave 256-row tiles under split-K
-T19 = os.environ.get("FRIDO_TUNE_T19", "1") != "0"                    # bf16x3: the 256 x 192 eight-wave tile is a candidate (A/B switch)
-# Time every candidate with COLD weights: in the sampler a GEMM's weights come from HBM (0.8 GB of them stream through the
-# 256 MB MALL per forward) while its activations were just written; timed back to back on one buffer the weights sit in L2 /
-# MALL instead.  With this on, consecutive repetitions read different copies of the weight operand out of a >= 320 MB ring.
-COLD_B = os.environ.get("FRIDO_TUNE_COLD_B", "0") != "0"
-# who adds split-K partial sums (FridoGemm.sk_mode): 0 = the splitk_reduce launch, 1 = the last workgroup of each tile, in-kernel
-SK_MODE = int(os.environ.get("FRIDO_SPLITK_MODE", "0"))
 CACHE_FILE = os.environ.get("FRIDO_TUNE_CACHE", "")
 # what to do with a GEMM signature the (pinned) cache does not hold: "tune" = time the candidates now (default); "static" = the
 # library's static heuristic (tile 0, no split-K) -- the GPU test suite runs this way (tests/conftest.py): benchmark shapes get the
 # benchmark's pinned tiles, every other shape a deterministic one, so a run of the suite is bitwise repeatable on any box
 ON_MISS = os.environ.get("FRIDO_TUNE_ON_MISS", "tune")
 _dirty = False
-# measured (profiles/r06_kg2_*, r06_tune_in_context.log): the back-to-back microbenchmark prefers a KG2 tile on 11 signatures (e.g. 4096 x 576 x 576: 22.7 -> 21.8 us),
-# IN CONTEXT the 4-wave tile wins them back (-5 ... -9 % per launch) and end to end the two caches tie (3.362 vs 3.368 images/s): OFF by default
-KG2 = os.environ.get("FRIDO_TUNE_KG2", "0") != "0"
-TILES_KG2 = (31, 33, 34, 35, 36)
-KG2_DIMS = {31: (128, 128), 33: (64, 64), 34: (128, 64), 35: (64, 192), 36: (64, 128)}
-KG2_MAX_WG = int(os.environ.get("FRIDO_TUNE_KG2_MAX_WG", "640"))
+# Not candidates: tiles 31 .. 36 (K split over the two wave groups of one workgroup).  Back to back they win 11 signatures, in context
+# the 4-wave tiles win them back and end to end the two caches tie (profiles/r06_kg2_*); tools/tune_in_context.py tries them on request.
 
 
 def _lib_tag():
     if os.environ.get("FRIDO_TUNE_TAG"):      # A/B of two library builds with the SAME pinned tiles (tools/ab.sh lib)
         return os.environ["FRIDO_TUNE_TAG"]
-    mode = f"+sk{SK_MODE}" if SK_MODE else ""       # tiles tuned under another split-K reduction are not comparable
     try:
         import hashlib
         # content hash of the DEFAULT (fp16-pair) build: two builds of equal size must not share pinned tiles.  (r06, advisor) NOT the
@@ -52,7 +38,7 @@ def _lib_tag():
         # persisted), and _load_cache runs once, at the first GEMM a process plans: were that a bf16-pair model, the pinned file would be
         # rejected for the whole process and could be overwritten at exit
         with open(_lib.LIB_PATHS["f16"], "rb") as f:
-            return hashlib.sha256(f.read()).hexdigest()[:16] + mode
+            return hashlib.sha256(f.read()).hexdigest()[:16]
     except OSError:
         return "?"
 
@@ -128,9 +114,6 @@ def workspace(device, nbytes, tag=""):
     return t.data_ptr()
 
 
-_rot = [0]
-
-
 def signature(st):
     """Cache key of a filled FridoGemm descriptor (pointers only as present / absent)."""
     sig = tuple(getattr(st, f) for f in _SIG_FIELDS) + (bool(st.residual), bool(st.out_f32), bool(st.out_op),
@@ -169,10 +152,7 @@ def best_tile(st, device, stream):
     b_elems = st.batch * max(st.b_bs, st.b_bs2, st.N * st.ldb) if (st.b_bs or st.b_bs2) else st.N * st.ldb
     a_elems, b_elems = (a_elems + 7) // 8 * 8, (b_elems + 7) // 8 * 8
     t.A, t.a_lo = _buf("A", a_elems * 2 * ns, device), a_elems
-    b_bytes = b_elems * 2 * ns
-    nrot = max(1, min(64, -(-(320 << 20) // b_bytes))) if COLD_B and st.batch == 1 else 1      # batched B operands are activations
-    b_base = _buf("B", b_bytes * nrot, device)
-    t.B, t.b_lo = b_base, b_elems
+    t.B, t.b_lo = _buf("B", b_elems * 2 * ns, device), b_elems
     if st.K2:
         a2 = (st.M * st.lda2 + 7) // 8 * 8
         t.A2, t.a2_lo = _buf("A2", a2 * 2 * ns, device), a2
@@ -204,36 +184,20 @@ def best_tile(st, device, stream):
         splits = [1]          # the split-K reduction writes rows in order; phase convs interleave them
     for sk in splits:
         t.splitk = sk
-        t.sk_mode = SK_MODE
+        t.sk_mode = 0        # partial sums are added by the splitk_reduce launch (or by the consuming GroupNorm: builder._deferred_splitk)
         t.ws = workspace_for(t, device) if sk > 1 else None
-        # BK = 64 halves the barrier count but costs a ring stage of occupancy: it only wins on small-M shapes
-        k64 = (st.nsplit == 1 and st.K % 64 == 0 and st.K2 % 64 == 0 and (not st.conv or st.Cin % 64 == 0) and (st.K // 64) >= sk
-               and (st.M * st.batch <= 4096 or K64_ALL))
-        big = (sk == 1 or BIG_SPLITK) and st.M >= 512 and st.N >= 96
+        # BK = 64 halves the barrier count but costs a ring stage of occupancy: tried on every one-plane shape it applies to
+        k64 = st.nsplit == 1 and st.K % 64 == 0 and st.K2 % 64 == 0 and (not st.conv or st.Cin % 64 == 0) and (st.K // 64) >= sk
+        big = st.M >= 512 and st.N >= 96
         # tile 9 = patch-staged 3x3 kernel (igemm.hip patch_ok; the library rejects it when it does not apply)
         patch = (st.conv and st.nsplit == 1 and st.batch == 1 and st.kh == 3 and st.stride == 1 and not (st.up_shift or st.dn_shift)
                  and not st.up2_phase and st.M % 128 == 0 and st.M >= 4096 and st.N >= 96 and sk <= (st.Cin + st.K2) // 32)
-        big_tiles = (TILES8W if st.nsplit == 1 else ((7, 18, 19) if T19 else (7, 18))) if big else ()  # bf16x3: 256 x 128 and the 8-wave 128 x 192 / 256 x 192
-        # (r06) tiles 31 / 33 / 34 / 35 / 36: K split over the two wave groups of ONE 8-wave workgroup (igemm.hip Geo, KG = 2) -- for dense
-        # two-plane launches that leave the chip under-filled (an even number of k-tiles, no split-K); the library rejects the rest
-        kg2 = TILES_KG2 if (KG2 and st.nsplit == 2 and not st.conv and sk == 1 and nk >= 2 and nk % 2 == 0 and not st.gn_x1) else ()
-        for tile in TILES + (TILES64 if k64 else ()) + big_tiles + ((17,) if big and k64 else ()) + ((9, 10) if patch else ()) + kg2:
+        big_tiles = (TILES8W if st.nsplit == 1 else (7, 18, 19)) if big else ()  # bf16x3: 256 x 128 and the 8-wave 128 x 192 / 256 x 192
+        for tile in TILES + (TILES64 if k64 else ()) + big_tiles + ((17,) if big and k64 else ()) + ((9, 10) if patch else ()):
             if tile % 10 in (1, 2, 4) and st.M < 64:
                 continue
-            if tile > 30 and -(-st.M // KG2_DIMS[tile][0]) * -(-st.N // KG2_DIMS[tile][1]) * st.batch > KG2_MAX_WG:
-                continue        # one 8-wave workgroup per CU: beyond ~two rounds the two-per-CU 4-wave form of the same tile wins
             t.tile = tile
-            if nrot > 1:
-                ops = []
-                for _ in range(reps + 1):
-                    u = G()
-                    C.memmove(C.addressof(u), C.addressof(t), C.sizeof(G))
-                    u.B = b_base + (_rot[0] % nrot) * b_bytes
-                    _rot[0] += 1
-                    ops.append((kind, u))
-                arr = _lib.pack_ops(ops)
-            else:
-                arr = _lib.pack_ops([(kind, t)] * (reps + 1))
+            arr = _lib.pack_ops([(kind, t)] * (reps + 1))
             ms = (C.c_float * (reps + 1))()
             rc = L.frido_run_timed(C.addressof(arr), reps + 1, stream, ms)
             if rc != 0:

@@ -17,7 +17,6 @@ from .builder import Builder, ACT_NONE, ACT_RELU, ACT_SILU
 from .engine import pack_matrix, rup
 
 import os
-CHAIN_FF = os.environ.get("FRIDO_CHAIN_FF", "1") != "0"     # FF2 + proj_out of a transformer block as one GEMM (A/B switch)
 # ERROR-BUDGET EXPERIMENTS (tools/x3_single_plane_table.py, profiles/r03_x3_single_plane_table.txt): keep ONE bf16 plane of an operand
 # class inside the bf16x3 mode.  Off by default -- every one of them fails the parity bar.
 X3_SPADE_BF16 = os.environ.get("FRIDO_X3_SPADE_BF16", "0") != "0"       # hoisted SPADE gamma / beta maps stored as bf16
@@ -243,20 +242,20 @@ class UNetStagePlan:
         n1, g1, be1 = self._norm_params(pre + ".in_layers.0")
         n2, g2, be2 = self._norm_params(pre + ".out_layers.0")
         bf16_maps = any(getattr(m, "bf16", False) for m in (g1, g2) if m is not None)
-        t1, sk1 = (0, 1) if bf16_maps else b.gn_conv_tile(x1, x2, self.Bx, h, w, blk.cout)
+        t1 = 0 if bf16_maps else b.gn_conv_tile(x1, x2, self.Bx, h, w, blk.cout)
         if t1 and has_skip:
             Craw = x1.C + (x2.C if x2 is not None else 0)
             if Craw % 64:
                 t1 = 0
-        t2, sk2 = b.gn_conv_tile(_Shape(blk.cout), None, self.Bx, h, w, blk.cout, raw=(x1, x2) if has_skip else None) if t1 else (0, 1)
+        t2 = b.gn_conv_tile(_Shape(blk.cout), None, self.Bx, h, w, blk.cout, raw=(x1, x2) if has_skip else None) if t1 else 0
         if t1 and t2:
-            hmid = b.gn_conv(t1, x1, x2, self.Bx, h, w, n1, 1e-5, pre + ".in_layers.2", gamma=g1, beta=be1, rowvec=rv, splitk=sk1)
+            hmid = b.gn_conv(t1, x1, x2, self.Bx, h, w, n1, 1e-5, pre + ".in_layers.2", gamma=g1, beta=be1, rowvec=rv)
             if has_skip:
                 out = b.gn_conv(t2, hmid, None, self.Bx, h, w, n2, 1e-5, pre + ".out_layers.3", gamma=g2, beta=be2,
-                                skip=(x1, x2, pre + ".skip_connection"), splitk=sk2)
+                                skip=(x1, x2, pre + ".skip_connection"))
             else:
                 assert x2 is None
-                out = b.gn_conv(t2, hmid, None, self.Bx, h, w, n2, 1e-5, pre + ".out_layers.3", gamma=g2, beta=be2, residual=x1, splitk=sk2)
+                out = b.gn_conv(t2, hmid, None, self.Bx, h, w, n2, 1e-5, pre + ".out_layers.3", gamma=g2, beta=be2, residual=x1)
             hmid.free()
             return out
         a1, raw = self._norm(x1, x2, HW, pre + ".in_layers.0", 1e-5, ACT_SILU, want_raw=has_skip)
@@ -306,13 +305,8 @@ class UNetStagePlan:
         vT = self._vt_self[(C, HW)]
         # the single-head output projection is folded into V: PV lands directly on the residual stream
         wvo, bvo = b.folded_vo_weight(t + ".attn1.to_v", t + ".attn1.to_out.0")
-        # the value and query projections both read n1 and are independent: V^T goes to the executor's side stream (a parallel
-        # branch of the captured graph), q' stays on the main one; they join before the attention core
-        b.prog.sync(0, 1)
-        with b.prog.side():
-            b.v_transposed(n1, C, wvo, Bx, HW, C, out=vT)
+        b.v_transposed(n1, C, wvo, Bx, HW, C, out=vT)
         qp = b.linear(n1, None, wop=wq, bias=False, out="op")
-        b.prog.sync(1, 0)
         h2 = b.attention(qp, C, n1, C, vT, Bx, HW, HW, C, bias_ptr=bvo, residual=hcur, stream=True, ln=(t + ".norm2", 1e-5))
         qp.free()
         n1.free()
@@ -322,7 +316,7 @@ class UNetStagePlan:
         if n2 is None:
             n2 = b.layernorm(h2, t + ".norm2")
         kc, vTc, bvo2 = self.kv[(pre, dpt)]     # kc = ctx (W_q^T W_k)^T: the query projection is folded into the cached keys
-        chain = last and CHAIN_FF and C % 64 == 0       # proj_out(h3 + ff2(gg)) + x in ONE GEMM (needs h3 as an operand along K)
+        chain = last and C % 64 == 0       # proj_out(h3 + ff2(gg)) + x in ONE GEMM (needs h3 as an operand along K)
         # (r05) with FF2 + proj_out chained, h3 is read only as an operand (A2 of that GEMM) and through norm3: where the kernel
         # produces both copies itself the f32 rows are not stored at all
         h3 = b.attention(n2, C, kc, C, vTc, Bx, HW, self.nctx, C, bias_ptr=bvo2, residual=h2, stream=True, also_op=chain,
@@ -381,21 +375,16 @@ class UNetStagePlan:
                 wv, bv = wo @ wv, wo @ bv + b.h64(pre + ".proj_out.bias")
             b._wcache[key] = (pack_matrix(b.to_dev(wv), b.nsplit), b.to_dev(bv))
         wv_op, bv_dev = b._wcache[key]
-        # V^T and the q / k projection both read a0 and are independent: V^T goes to the executor's side stream
-        b.prog.sync(0, 1)
-        with b.prog.side():
-            b.v_transposed(a0, C, wv_op, Bx, HW, C, bias_ptr=None if heads == 1 else bv_dev.data_ptr(), out=vT)
+        b.v_transposed(a0, C, wv_op, Bx, HW, C, bias_ptr=None if heads == 1 else bv_dev.data_ptr(), out=vT)
         if heads == 1:
             # one head, any width: q | k = the first 2 C rows of the projection, the existing single-head kernels, proj_out folded
             # into V so that P V + bias + x lands on the residual stream
             qk = b.linear(a0, None, wop=b.lin_weight(pre + ".qkv.weight", rows=(0, 2 * C)), bias_ptr=b.bias(pre + ".qkv.bias"), out="op")
-            b.prog.sync(1, 0)
             out = b.attention(qk, 2 * C, qk, 2 * C, vT, Bx, HW, HW, C, q_off=0, k_off=C, bias_ptr=bv_dev.data_ptr(), residual=x, stream=True)
             qk.free()
             a0.free()
             return out
         qkv = b.linear(a0, pre + ".qkv", out="op")            # [Bx*HW][3 C]: q and k stay where the projection left them
-        b.prog.sync(1, 0)
         o = b.attention_heads(qkv, 3 * C, vT, Bx, HW, heads, d, legacy=not blk.new_order)
         qkv.free()
         a0.free()

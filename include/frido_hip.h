@@ -608,7 +608,7 @@ int frido_l2norm(const FridoL2Norm* d, frido_stream_t s);
 int frido_attn_flash(const FridoAttnSmall* d, frido_stream_t s);
 int frido_attn_flash_supported(int32_t d);
 /* (r05) head widths for which a two-plane frido_attn_flash launch may carry FridoAttnSmall.ln_op (its workgroups own whole rows):
- * 256 and 384 always, 512 on the d-split 8-wave form (the default; FRIDO_FLASH_DSPLIT=0 selects the 4-wave form). */
+ * 256, 384 and 512 (the d-split 8-wave form). */
 int frido_attn_flash_ln_supported(int32_t d);
 /* (ABI 7) Multi-head flash attention on a FridoAttnMh descriptor; frido_attn_mh_supported(d) tells whether a head dimension is
  * instantiated (32 and 64).  Unsupported arguments return FRIDO_EINVAL and launch nothing. */

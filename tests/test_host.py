@@ -78,6 +78,61 @@ def test_shipped_libraries_are_not_profiling_or_experiment_builds():
             assert name.encode() not in body, f"{path} still names the retired build-time variant {name}"
 
 
+RETIRED_SWITCHES = (
+    "FRIDO_UP2_PHASES", "FRIDO_GN_FUSED", "FRIDO_GN_CONV_TINY", "FRIDO_GN_EPI_STATS", "FRIDO_LN_IN_ATTN", "FRIDO_ATTN_FLASH",
+    "FRIDO_ATTN_FLASH_SHORT_NQ", "FRIDO_GN_CONV", "FRIDO_GN_CONV_SPLITK", "FRIDO_GN_CONV_PREFER", "FRIDO_ATTN_SKIP_DEAD_STREAM",
+    "FRIDO_GN_FUSED_MAX_HW", "FRIDO_ATTN_FLASH_MIN_KEYS", "FRIDO_SK_DEFER",       # still module constants of builder.py, no longer variables
+    "FRIDO_CHAIN_FF", "FRIDO_SIDE_STREAM", "FRIDO_STAGGER_MODE", "FRIDO_STAGGER_8W", "FRIDO_GEMM_PANELS",
+    "FRIDO_TUNE_K64_ALL", "FRIDO_TUNE_BIG_SPLITK", "FRIDO_TUNE_T19", "FRIDO_TUNE_COLD_B", "FRIDO_SPLITK_MODE", "FRIDO_TUNE_KG2",
+    "FRIDO_TUNE_KG2_MAX_WG", "FRIDO_FLASH_DSPLIT", "FRIDO_FLASH_NW8_MIN_WGS", "FRIDO_GN_FUSED_V4", "FRIDO_GN_FUSED_SK1024", "FRIDO_SERIAL",
+    "FRIDO_KORDER")
+
+
+def _library_sources():
+    """Every source file of the package (Python and csrc) and the C header."""
+    import glob
+    pkg = os.path.dirname(_lib.__file__)
+    files = glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True)
+    files += [f for f in glob.glob(os.path.join(pkg, "csrc", "*")) if f.endswith((".hip", ".h", "Makefile"))]
+    files.append(os.path.join(os.path.dirname(pkg), "include", "frido_hip.h"))
+    assert len(files) >= 40
+    return files
+
+
+def test_retired_environment_switches_are_named_nowhere_in_the_library():
+    """The run-time A/B switches whose experiments are closed (INTEGRATION.md "Retired switches") are gone from the library: no Python
+    file of frido_amd, no file of csrc and not the header names one of them (whole names: FRIDO_OP_GN_FUSED, the op kind, is another word)."""
+    import re
+    pat = re.compile(r"(?<![A-Za-z0-9_])(" + "|".join(RETIRED_SWITCHES) + r")(?![A-Za-z0-9_])")
+    for path in _library_sources():
+        hit = pat.search(open(path, encoding="utf-8").read())
+        assert hit is None, f"{path} still names the retired switch {hit.group(1)}"
+
+
+def test_environment_switches_read_are_the_documented_ones():
+    """The FRIDO_* variables the library reads (os.environ in frido_amd/**/*.py, getenv in csrc) are exactly the ones in the table of
+    INTEGRATION.md "Environment switches", minus the documented ones that only bench.py or the tools read."""
+    import re
+    read = set()
+    for path in _library_sources():
+        text = open(path, encoding="utf-8").read()
+        if path.endswith(".py"):
+            read |= set(re.findall(r"os\.environ(?:\.get\(|\[|\.setdefault\()\s*[\"'](FRIDO_[A-Z0-9_]+)[\"']", text))
+            read |= set(re.findall(r"[\"'](FRIDO_[A-Z0-9_]+)[\"']\s+(?:not\s+)?in\s+os\.environ", text))
+        else:
+            read |= set(re.findall(r"getenv\(\s*\"(FRIDO_[A-Z0-9_]+)\"", text))
+    doc = open(os.path.join(os.path.dirname(os.path.dirname(_lib.__file__)), "INTEGRATION.md"), encoding="utf-8").read()
+    table = doc.split("## Environment switches")[1].split("###")[0]
+    documented = set()
+    for row in table.splitlines():
+        if row.startswith("| `FRIDO_"):
+            documented |= set(re.findall(r"`(FRIDO_[A-Z0-9_]+)`", row.split("|")[1]))
+    outside = {"FRIDO_BENCH_STUB", "FRIDO_DEBUG_SKIP"}      # read by bench.py / tools/debug_skip.py only
+    assert outside <= documented and not (outside & read)
+    assert len(read) >= 15 and read == documented - outside, (sorted(read - documented), sorted(documented - outside - read))
+    assert not (documented & set(RETIRED_SWITCHES))
+
+
 def test_bad_descriptors_are_rejected_without_touching_a_device():
     L = _lib.lib()
     kind, st = _lib.make_op("FRIDO_OP_GEMM", M=16, N=16, K=20, batch=1, nsplit=1)     # K not a multiple of 32

@@ -8,8 +8,9 @@
 #   tools/ab.sh lib   A.so B.so [C.so ...] builds of the library, all on the FIRST one's pinned tiles (FRIDO_TUNE_TAG)
 #   tools/ab.sh libtuned A.so B.so ...     builds of the library, each with its own tuning
 #   ROUNDS=3 (default 2)   EXTRA="--batch 32" (more bench.py flags)
-# Recipes of committed profiles: r06_stagger_*: `tools/ab.sh env FRIDO_STAGGER_US 0 4 8 12`; r06_kg2_end_to_end_ab: `tools/ab.sh tuned FRIDO_TUNE_KG2 1 0`;
-# r05_gn_fused_v4_ab: `tools/ab.sh env FRIDO_GN_FUSED_V4 1 0`; r04_x3_side_stream_ab: `tools/ab.sh env FRIDO_SIDE_STREAM 0 1`.
+# Recipes of committed profiles: r06_stagger_*: `tools/ab.sh env FRIDO_STAGGER_US 0 4 8 12`.  The switches of r06_kg2_end_to_end_ab
+# (`tuned FRIDO_TUNE_KG2 1 0`), r05_gn_fused_v4_ab (`env FRIDO_GN_FUSED_V4 1 0`) and r04_x3_side_stream_ab (`env FRIDO_SIDE_STREAM 0 1`) are RETIRED
+# (INTEGRATION.md "Retired switches"): those recipes need a checkout of the commit before their removal.
 MODE=${1:?env | tuned | lib | libtuned}; shift
 ROUNDS=${ROUNDS:-2}
 B="--steps 2 --warmup 1 --full --no-cpu-baseline --no-bf16-extra --no-other-configs $EXTRA"

@@ -4,14 +4,14 @@
 #   tools/gemm_sweep.sh [-n NSPLIT] [-t TILES] [-v "ENVVAR v1 v2 ..."]... (-p PRESET | "shape" ...)
 #     -n  1 = bf16, 2 = two-plane arithmetic (default 2)          -t  comma-separated tile ids (default 1,2,3,4,5,6,7)
 #     -v  sweep an environment variable of gemm_bench.py / the library over values (may repeat: nested loops), e.g.
-#         "SPLITK 1 2 4 8", "NOEPI 0 2 4 1", "SKMODE 0 1", "FRIDO_GEMM_FLAGS 0 128", "FRIDO_KORDER 1 0"
+#         "SPLITK 1 2 4 8", "NOEPI 0 2 4 1", "SKMODE 0 1", "FRIDO_GEMM_FLAGS 0 128"
 #     a shape is gemm_bench.py's own spelling: "conv B H W Cin Cout" | "dense M N K" | "geglu M N K"
 # Presets (the shape lists the old scripts carried):
 #   denoiser  the top shapes of a layout2i forward at B = 16        dense     the dense / GEGLU shapes of the 32^2 and 16^2 planes
 #   conv      the 64^2 / 32^2 / 16^2 3x3 convs                       smallm    the 8^2 / 16^2 convs that run under split-K
 #   t19       the shapes the 256 x 192 eight-wave tile competes on
 # Recipes of the committed profiles:  r03_x3_tiles_*: -t 1,2,4,5,6,3,7 -p denoiser   |   r03_ab_kwalk_rotation: -t 7,1,2
-#   -v "FRIDO_GEMM_FLAGS 0 128" -p denoiser   |   r03_x3_korder_ab: -t 1,2,7 -v "FRIDO_KORDER 1 0" -p conv   |   r03_x3_splitk_inkernel_ab: -t 1,3,4,6,7,18
+#   -v "FRIDO_GEMM_FLAGS 0 128" -p denoiser   |   r03_x3_splitk_inkernel_ab: -t 1,3,4,6,7,18
 #   -v "SPLITK 2 4 8" -v "SKMODE 0 1" -p smallm   |   r03_x3_tile19_ab: -t 2,7,18,19 -p t19   |   r02_gemm_k_sweep*: -n 1 -v "NOEPI 0 1" with explicit K ladders
 NS=2; TILES=1,2,3,4,5,6,7; VARS=(); PRESET=""
 while getopts "n:t:v:p:" o; do
