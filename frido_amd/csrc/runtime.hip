@@ -326,6 +326,7 @@ extern "C" int frido_sizeof_desc(int32_t kind) {
         case FRIDO_OP_L2NORM: return sizeof(FridoL2Norm);
         case FRIDO_OP_ATTN_MH: return sizeof(FridoAttnMh);
         case FRIDO_DESC_KEEP_BLEND: return sizeof(FridoKeepBlend);
+        case FRIDO_DESC_INVERT_STEP: return sizeof(FridoInvertStep);
         default: return -1;
     }
 }

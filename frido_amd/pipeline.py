@@ -126,3 +126,23 @@ def edit_images(model, images, cond, *, S, strength, keep_mask=None, eta=1.0, sc
         from . import _lib
         _lib.warn_on_status("edit_images")
     return all_gather_images(img, total=total) if gather else img
+
+
+@torch.no_grad()
+def invert_images(model, images, cond, *, S, t_start=None, strength=None, scale=1.0, uncond=None, first_stage=0, num_stage=None, sample0=0,
+                  gather=True, total=None, log_every_t=10 ** 9, check_status=True):
+    """DDIM inversion of this rank's shard: images (b, 3, H, W) in [-1, 1] on the GPU -> encode_first_stage + get_first_stage_encoding ->
+    DDIMSampler.invert (the first k of S rows per stage, k = t_start or clamp(int(strength * S), 1, S)).  Returns the inverted latents
+    x_inv (gathered), to hand to DDIMSampler.edit(S, z0, c, init="noise", x_T=x_inv, t_start=k, first_stage=first_stage, eta=0).
+    Every sample is inverted on its own and nothing is drawn, so a shard of the batch equals the same rows of the whole batch whatever
+    its global sample index `sample0` is; gather / total / check_status as in edit_images."""
+    from .samplers import DDIMSampler
+    unet = model.model.diffusion_model
+    z0 = model.get_first_stage_encoding(model.encode_first_stage(images))
+    x_inv, _ = DDIMSampler(model).invert(S, z0, cond, t_start=t_start, strength=strength, first_stage=first_stage,
+                                         num_stage=num_stage or unet.num_stage, unconditional_guidance_scale=scale,
+                                         unconditional_conditioning=uncond, log_every_t=log_every_t, verbose=False)
+    if check_status and x_inv.is_cuda:
+        from . import _lib
+        _lib.warn_on_status("invert_images")
+    return all_gather_images(x_inv, total=total) if gather else x_inv

@@ -6,7 +6,8 @@
                      kind), a device step counter and coefficient tables
                      (reference: frido/models/diffusion/ddim.py:116-273, plms.py:116-303); kind="ddpm": the
                      ancestral loop of frido/models/diffusion/frido.py:1308-1418 on the same machinery; kind="dpm":
-                     DPM-Solver++(2M), which the reference does not have, in DDIM's loop (frido_dpm_step as the update);
+                     DPM-Solver++(2M), which the reference does not have, in DDIM's loop (frido_dpm_step as the update); kind="invert":
+                     DDIM's deterministic encoder, the chain walked upwards from a clean latent (frido_invert_step as the update);
   ancestral_step   — one ancestral update outside a loop (FridoDiffusion.p_mean_variance / p_sample);
   DecoderRuntime   — VQModelInterface.decode / decode_first_stage on the HIP engine; MSFPNVQModel's encode_quant / decode_quant /
                      reconstruct (encode program, codebook loss and decode program as one captured graph).
@@ -21,7 +22,8 @@ from . import _lib, config
 from .builder import Builder
 from .engine import Prog, current_stream_ptr, own_stream, require_gpu
 from .patching import FOREIGN, PatchProg
-from .schedules import ancestral_table, dpm_solver_table, sampler_coef_table
+from .schedules import (ancestral_table, ddim_inversion_table, dpm_solver_table, make_ddim_sampling_parameters, make_ddim_timesteps,
+                        sampler_coef_table)
 from .unet_plan import UNetStagePlan
 from .vqgan_plan import VQDecodePlan, VQDecodeQuantPlan, VQEncodePlan
 
@@ -32,6 +34,8 @@ DPM_STEP = "dpm_step"
 FOREIGN[DPM_STEP] = "frido_dpm_step"      # op tag of the DPM-Solver++ update inside a step body (patching.PatchProg)
 KEEP_BLEND = "keep_blend"
 FOREIGN[KEEP_BLEND] = "frido_keep_blend"  # op tag of the editing blend (csrc/edit.hip) in front of a model evaluation
+INVERT_STEP = "invert_step"
+FOREIGN[INVERT_STEP] = "frido_invert_step"  # op tag of the DDIM inversion update (csrc/invert.hip)
 EDIT_RNG_STREAM = 64                      # Philox stream of stage s's blend draws: 64 + s, apart from 0 (x_T) and 1 .. num_stage (the updates)
 
 
@@ -301,6 +305,14 @@ class SamplerEngine:
             # DPM-Solver++(2M): the grid (skip_type) is part of the solver; every stage walks the table from row 0, a first-order row
             assert patch is None, "the DPM-Solver loop has no patch-wise mode"
             self.t_loop, tab = dpm_solver_table(np.asarray(alphas_cumprod, dtype=np.float64), S, skip_type, order, lower_order_final)
+        elif kind == "invert":
+            # DDIM's chain walked UPWARDS: row i = the sampler's ddim_alphas / ddim_alphas_prev / ddim_timesteps at index i, so the
+            # time-embedding rows and the coefficient rows ascend together and the device counter still only increments
+            assert patch is None, "the inversion loop has no patch-wise mode"
+            ac32 = np.asarray(alphas_cumprod, dtype=np.float32)
+            self.t_loop = make_ddim_timesteps("uniform", S, len(ac32))
+            _, al, alp = make_ddim_sampling_parameters(ac32, self.t_loop, 0.0)
+            tab = ddim_inversion_table(al, alp)
         else:
             tab, self.t_loop = sampler_coef_table(np.asarray(alphas_cumprod, dtype=np.float32), S, eta, plms=(kind == "plms"))
         self.n_steps = S if kind == "ddpm" else tab.shape[0]
@@ -402,6 +414,11 @@ class SamplerEngine:
         already guidance-mixed (a score corrector ran)."""
         B, HW, C = self.B, self.H * self.W, self.C
         start, nch, eps = sum(self.embed[:s]), self.embed[s], self._eps_ptr(s)
+        if self.kind == "invert":       # (INVERT_STEP, FridoInvertStep): the stage's window only, no noise, no x0
+            return INVERT_STEP, _lib.STRUCTS["FridoInvertStep"](
+                x=self.x.data_ptr(), eps_cond=eps, eps_uncond=eps + 4 * B * HW * nch if self.xrep == 2 else None, cfg_scale=self.cfg_scale,
+                cfg_dev=self.cfg_dev.data_ptr(), coef=self.coef.data_ptr(), step=self.step.data_ptr(), B=B, HW=HW, Cx=C, c_lo=start,
+                c_hi=start + nch)
         kw = dict(x=self.x.data_ptr(), B=B, HW=HW, Cx=C, start=start, nch=nch, eps_cond=eps, coef=self.coef.data_ptr(),
                   step=self.step.data_ptr(), x_out=self.x.data_ptr(), pred_x0=self.pred_x0.data_ptr())
         if self.kind != "ddpm":
@@ -563,6 +580,7 @@ class SamplerEngine:
         hand-off: what an adopted x_T gets), and x_T is only the start state of init="noise", it adopts nothing by itself.
         Returns (samples NCHW, intermediates dict)."""
         assert self.kind != "ddpm", "an ancestral engine runs through run_ancestral()"
+        assert self.kind != "invert", "an inversion engine runs through run_invert()"
         if edit is not None:
             assert self.kind == "ddim" and self.geo is None, "editing is built for the whole-latent DDIM engine"
             assert noise_dropout == 0. and score_corrector is None, "an edit has no noise_dropout / score_corrector"
@@ -647,6 +665,48 @@ class SamplerEngine:
         key = ("dpm" if self.kind == "dpm" else "ddim_tape" if noise else "ddim", s)
         self._body(key, sp, lambda: [self._eval_ops(s), self._update_op(s, noise), 1])
         self._replay(key, self._unit_steps(o, GRAPH_STEPS), logged_at(n, o.log_every_t), sp, after_unit=log)
+
+    # ---- DDIM inversion: the chain walked upwards from a clean latent -----------------------------------------------------------
+    @torch.no_grad()
+    @_lib.with_planes
+    def run_invert(self, z0, k, cond, uncond=None, *, first_stage=0, log_every_t=100, callback=None):
+        """DDIM's deterministic encoder: every stage s >= first_stage starts from the clean latent z0 (B, C, H, W) -- the earlier stages'
+        channels clean, its own window [a_s, e_s) to be noised: the state its denoiser was trained on -- and runs the FIRST k rows of the
+        ascending table, x' = c0 x + c1 eps on the window (frido_invert_step), eps at ddim_timesteps[i].  The stages do not depend on one
+        another: no hand-off, every stage reads z0.  One captured body per stage ([evaluation, update, +1]) replayed in units of up to
+        GRAPH_STEPS; z0 and k are device state or loop bounds, so every z0 / k / guidance scale replays the same graphs.  No noise is
+        drawn.  Returns (x_inv NCHW: z0's bits below first_stage, every other window its stage's inverted state -- what
+        run(edit=EditSpec(init="noise"), x_T=x_inv) starts its last k rows from --, {"x_inter": [z0, logged states ...]})."""
+        assert self.kind == "invert", "run_invert() is the inversion engine's loop"
+        assert 1 <= k <= self.n_steps and 0 <= first_stage < self.num_stage, (k, first_stage)
+        B, C, H, W = self.B, self.C, self.H, self.W
+        o = SimpleNamespace(callback=callback, img_callback=None)
+        logged = logged_at(k, log_every_t)
+        with own_stream(self, self.dev) as sp:
+            ctx = self._context(cond, uncond)
+            self.cfg_dev.fill_(self.cfg_scale)
+            z = z0.to(self.dev, torch.float32).contiguous()
+            assert z.shape == (B, C, H, W), (tuple(z.shape), (B, C, H, W))
+            if not hasattr(self, "z0"):
+                self.z0 = torch.zeros_like(self.x)
+            _relayout(self.b, sp, z, self.z0, B, H * W, C, 0)
+            out, inter = z.clone(), {"x_inter": [z.clone()]}
+            t_loop = torch.from_numpy(self.t_loop.astype(np.int64)).to(self.dev)
+            for s in range(first_stage, self.num_stage):
+                a, e = sum(self.embed[:s]), sum(self.embed[:s + 1])
+                self.x.copy_(self.z0)
+                self._bind_stage(s, ctx, t_loop, sp)
+
+                def log(i, e=e):
+                    if callback:
+                        callback(i)
+                    if logged(i):
+                        inter["x_inter"].append(self._to_nchw(self.x, sp)[:, :e])
+                key = ("invert", s)
+                self._body(key, sp, lambda: [self._eval_ops(s), self._update_op(s), 1])
+                self._replay(key, self._unit_steps(o, GRAPH_STEPS), logged, sp, after_unit=log, n=k)
+                out[:, a:e] = self._to_nchw(self.x, sp)[:, a:e]       # plumbing: the stage's window into the result
+        return out, inter
 
     # ---- editing: img2img start and keep-mask inpainting in DDIM's loop ---------------------------------------------------------
     def _bind_edit(self, ed, sp):

@@ -81,21 +81,24 @@ class _SamplerBase:
             raise ValueError("ddim_eta must be 0 for PLMS")
         ac = self.model.alphas_cumprod.detach().float().cpu().numpy()
         assert ac.shape[0] == self.ddpm_num_timesteps, "alphas have to be defined for each timestep"
+        self.ddim_num_steps = ddim_num_steps
         self.ddim_timesteps = schedules.make_ddim_timesteps(ddim_discretize, ddim_num_steps, self.ddpm_num_timesteps)
         sig, al, alp = schedules.make_ddim_sampling_parameters(ac, self.ddim_timesteps, ddim_eta)
         self.ddim_sigmas, self.ddim_alphas, self.ddim_alphas_prev = sig, al, alp
         self.ddim_sqrt_one_minus_alphas = np.sqrt((np.float32(1.0) - al).astype(np.float32))
         self.alphas_cumprod = ac
 
-    def _engine(self, B, shape, nctx, S, eta, scale, num_stage, temperature, replica=0, patch=None, solver=None):
+    def _engine(self, B, shape, nctx, S, eta, scale, num_stage, temperature, replica=0, patch=None, solver=None, kind=None):
         """The cached SamplerEngine of this call.  solver: DPM-Solver++'s (order, skip_type, lower_order_final), part of its engine's key where
-        DDIM / PLMS have eta and the temperature; its table is computed from the float64 schedule."""
+        DDIM / PLMS have eta and the temperature; its table is computed from the float64 schedule.  kind: another loop of this sampler
+        ("invert": DDIMSampler.invert), with engines -- plans, tables, graphs -- of its own under its own key."""
+        kind = kind or self.KIND
         from .runtime import SamplerEngine
         unet = self.model.model.diffusion_model
         rt = unet.runtime()
         C, H, W = shape
         if solver is None:
-            key = (self.KIND, B, C, H, W, nctx, S, float(eta), scale != 1.0, num_stage, float(temperature), replica)
+            key = (kind, B, C, H, W, nctx, S, float(eta), scale != 1.0, num_stage, float(temperature), replica)
             more, ac = dict(temperature=temperature, patch=patch), self.model.alphas_cumprod.detach().float()
         else:
             key = (self.KIND, B, C, H, W, nctx, S, scale != 1.0, num_stage, replica) + solver
@@ -104,7 +107,7 @@ class _SamplerBase:
             from .patching import geometry_key
             key += (geometry_key(patch),)
         eng = cached_engine(rt, key, lambda: SamplerEngine(
-            rt.builder_for(replica), unet.cfg, B=B, C=C, H=H, W=W, nctx=nctx if isinstance(nctx, int) else 0, S=S, eta=eta, kind=self.KIND,
+            rt.builder_for(replica), unet.cfg, B=B, C=C, H=H, W=W, nctx=nctx if isinstance(nctx, int) else 0, S=S, eta=eta, kind=kind,
             alphas_cumprod=ac.cpu().numpy(), embed_dim=self.model.embed_dim_list, cfg_scale=scale, num_stage=num_stage, **more))
         eng.cfg_scale = float(scale)      # read from a device scalar by the captured step bodies: one graph, any scale
         return eng
@@ -242,6 +245,63 @@ class _SamplerBase:
                            log_every_t=log_every_t, callback=callback, img_callback=img_callback, model=self.model, edit=spec)
         from . import autoplanes
         return autoplanes.run(self.model.model.diffusion_model, go, f"{type(self).__name__}.edit", noise=noise)
+
+    @torch.no_grad()
+    def invert(self, S, z0, conditioning=None, *, t_start=None, strength=None, first_stage=0, num_stage=1,
+               unconditional_guidance_scale=1., unconditional_conditioning=None, log_every_t=100, callback=None, verbose=True, replica=0,
+               score_corrector=None):
+        """DDIM inversion (DDIM's deterministic encoder; upstream latent-diffusion's DDIMSampler.encode, not in the reference): walk the
+        probability-flow ODE UPWARDS from the clean latent z0 (B, C, H, W) through the first k rows of the S-step grid,
+        k = t_start or clamp(int(strength * S), 1, S) -- the rows `edit` counts from the chain's end.  Row i, evaluated at
+        ddim_timesteps[i], is x' = sqrt(a / p) x + sqrt(a) (sqrt(1 / a - 1) - sqrt(1 / p - 1)) eps with a = ddim_alphas[i],
+        p = ddim_alphas_prev[i] (schedules.ddim_inversion_table): the exact inverse of the eta = 0 update of that row for the same eps.
+        Every stage from `first_stage` on inverts its own channels [a_s, e_s) from z0[:, :e_s] (earlier stages clean, its window noised:
+        what its denoiser reads); the stages do not depend on one another.  Returns (x_inv, {"x_inter": [...]}): x_inv has z0's bits
+        below first_stage and every other window at level ddim_alphas[k - 1], where
+        `edit(S, z0, c, init="noise", x_T=x_inv, t_start=k, first_stage=f, eta=0)` starts -- with the same conditioning it comes back to
+        z0 up to the discretisation error, with another one it edits.  Deterministic: no generator is touched.
+        PLMS / DPM-Solver inversion, split_input_params, score_corrector and dict / list conditionings are refused by name."""
+        no = lambda what: NotImplementedError(f"{type(self).__name__}.invert: {what} is not built for inversion")
+        if self.KIND != "ddim":
+            raise no(f"{type(self).__name__} (inversion walks DDIM's chain: use DDIMSampler.invert)")
+        from . import patching
+        if patching.params_of(self.model) is not None:
+            raise no("split_input_params (the patch-wise mode)")
+        if score_corrector is not None:
+            raise no("score_corrector")
+        if isinstance(conditioning, (dict, list)) or isinstance(unconditional_conditioning, (dict, list)):
+            raise no("a dict / list conditioning")
+        k = edit_steps(S, t_start, strength)
+        if not 0 <= first_stage < num_stage:
+            raise ValueError(f"invert: first_stage={first_stage} must name one of the {num_stage} stages that run")
+        if not torch.is_tensor(z0) or z0.dim() != 4:
+            raise ValueError("invert: z0 is the (B, C, H, W) latent to invert")
+        B, shape = z0.shape[0], tuple(z0.shape[1:])
+        mode = self._check_guidance(conditioning, unconditional_conditioning, unconditional_guidance_scale, B)
+        if not z0.is_cuda:
+            raise FridoHipError("invert(): z0 must live on the MI355X (there is no CPU path)")
+        self.make_schedule(ddim_num_steps=S, ddim_eta=0., verbose=verbose)
+        if unconditional_guidance_scale != 1.:
+            assert unconditional_conditioning is not None
+        if verbose:
+            print(f"Data shape for DDIM inversion is {(B, *shape)}, the first {k} of {S} steps")
+        self.num_stage = num_stage
+
+        def go(_):
+            eng = self._engine(B, shape, mode, S, 0.0, unconditional_guidance_scale, num_stage, 1.0, replica, kind="invert")
+            return eng.run_invert(z0, k, conditioning, unconditional_conditioning, first_stage=first_stage, log_every_t=log_every_t,
+                                  callback=callback)
+        from . import autoplanes
+        return autoplanes.run(self.model.model.diffusion_model, go, f"{type(self).__name__}.invert")
+
+    def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None, unconditional_guidance_scale=1.0,
+               unconditional_conditioning=None, callback=None, **kwargs):
+        """Upstream latent-diffusion's argument order for `invert`: t_enc rows of the schedule last made (make_schedule(ddim_num_steps))."""
+        if use_original_steps or not hasattr(self, "ddim_num_steps"):
+            raise NotImplementedError(f"{type(self).__name__}.encode: call make_schedule(ddim_num_steps) first; use_original_steps (the "
+                                      "model's own chain) is not built for inversion")
+        return self.invert(self.ddim_num_steps, x0, c, t_start=t_enc, unconditional_guidance_scale=unconditional_guidance_scale,
+                           unconditional_conditioning=unconditional_conditioning, callback=callback, **kwargs)
 
 
 class DDIMSampler(_SamplerBase):

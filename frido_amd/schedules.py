@@ -108,6 +108,18 @@ def make_ddim_sampling_parameters(alphacums32, ddim_timesteps, eta):
     return sigmas, alphas, alphas_prev
 
 
+def ddim_inversion_table(alphas, alphas_prev):
+    """float32 table [n][2] = {c0, c1} of DDIM's deterministic encoder (the probability-flow ODE walked UPWARDS; upstream latent-diffusion's
+    DDIMSampler.encode, not in the reference), from the sampler's own ddim_alphas / ddim_alphas_prev (make_schedule(S, ddim_eta=0)).  Row i
+    moves the state from level p = alphas_prev[i] to a = alphas[i] with the eps evaluated at ddim_timesteps[i]:
+      x' = c0 x + c1 eps,   c0 = sqrt(a / p),   c1 = sqrt(a) (sqrt(1 / a - 1) - sqrt(1 / p - 1))
+    -- the exact inverse of the eta = 0 update of the same row with the same eps.  Rows ascend (i = 0 is the first one run); after k rows
+    the state sits at alphas[k - 1], where an edit of the chain's last k rows starts.  float64 throughout, rounded to float32 once."""
+    a, p = np.asarray(alphas, dtype=np.float64), np.asarray(alphas_prev, dtype=np.float64)
+    assert a.shape == p.shape and a.ndim == 1, (a.shape, p.shape)
+    return np.stack((np.sqrt(a / p), np.sqrt(a) * (np.sqrt(1.0 / a - 1.0) - np.sqrt(1.0 / p - 1.0))), axis=1).astype(np.float32)
+
+
 DPM_ROW = 8     # must match csrc/dpmstep.hip: inv_alpha, sigma, c_x, c_d, w_cur, w_last, pad x2
 DPM_SKIP_TYPES = ("logSNR", "time_uniform")
 

@@ -554,6 +554,25 @@ typedef struct FridoKeepBlend {
 /* frido_sizeof_desc() code of a descriptor that belongs to no op kind */
 #define FRIDO_DESC_KEEP_BLEND 1001
 
+/* ---- DDIM inversion: the deterministic encoder of DDIM (the probability-flow ODE walked upwards; upstream latent-diffusion's
+ * DDIMSampler.encode), not in the reference ----
+ * Not an op kind: an exported launcher with a descriptor of its own (frido_invert_step below), run eagerly or between frido_capture_begin
+ * and frido_capture_end.  One pass over the NHWC f32 state x[B][HW][Cx], in place, on the channel window [c_lo, c_hi) -- the stage's own
+ * channels; eps_cond / eps_uncond are the denoiser's output [B * HW][c_hi - c_lo].  {c0, c1} = coef[*step + coef_row_offset] of the 2-float
+ * rows of frido_amd/schedules.py ddim_inversion_table (step NULL reads as 0).  Per element in fp32, every product and sum rounded on its
+ * own (no contraction):
+ *   e  = eps_cond, or e_u + s (e_c - e_u) with eps_uncond, s = *cfg_dev if cfg_dev else cfg_scale   (FridoSamplerStep's expression)
+ *   x' = c0 x + c1 e
+ * Channels outside the window keep their bits (they are neither read nor written).  Any B, HW, Cx and window; scalar accesses.  A
+ * non-finite x' raises FRIDO_STATUS_NONFINITE. */
+typedef struct FridoInvertStep {
+    float* x; const float* eps_cond; const float* eps_uncond;
+    const float* cfg_dev;        /* optional device float overriding cfg_scale (graph replay) */
+    const float* coef; const int32_t* step;
+    int32_t B, HW, Cx, c_lo, c_hi, coef_row_offset; float cfg_scale;
+} FridoInvertStep;
+#define FRIDO_DESC_INVERT_STEP 1002
+
 enum FridoOpKind {
     FRIDO_OP_GEMM = 1, FRIDO_OP_GN_STATS, FRIDO_OP_GN_APPLY, FRIDO_OP_LAYERNORM, FRIDO_OP_SOFTMAX,
     FRIDO_OP_GEGLU, FRIDO_OP_PACK, FRIDO_OP_RELAYOUT, FRIDO_OP_VQ, FRIDO_OP_SAMPLER_STEP,
@@ -653,6 +672,9 @@ int frido_dpm_step(const FridoDpmStep* d, frido_stream_t s);
 /* ---- the editing blend (descriptor above); bad arguments return FRIDO_EINVAL before any device is touched ---- */
 int frido_keep_blend(const FridoKeepBlend* d, frido_stream_t s);
 
+/* ---- the DDIM inversion update (descriptor above); bad arguments return FRIDO_EINVAL before any device is touched ---- */
+int frido_invert_step(const FridoInvertStep* d, frido_stream_t s);
+
 /* ---- timing on the launch stream (HIP events) ---- */
 int frido_event_create(void** ev);
 int frido_event_record(void* ev, frido_stream_t s);
@@ -669,7 +691,7 @@ int frido_abi_version(void);
  * A host that packs weights / operands itself (hi = round(v), lo = round(v - hi) in this format) asks here. */
 int frido_x3_plane_format(void);
 int frido_sizeof_op(void);             /* sizeof(FridoOp): checked by the ctypes mirror */
-int frido_sizeof_desc(int32_t kind);   /* sizeof of the descriptor struct of that op kind (or of FRIDO_DESC_KEEP_BLEND) */
+int frido_sizeof_desc(int32_t kind);   /* sizeof of the descriptor struct of that op kind (or of FRIDO_DESC_KEEP_BLEND / FRIDO_DESC_INVERT_STEP) */
 const char* frido_last_error(void);
 /* Sticky numerics status of the CURRENT device (r05): kernels cannot return errors, so operand producers and normalisation kernels
  * OR bits into a device word when they meet a value the arithmetic cannot represent, and this call reads it back (it synchronises
