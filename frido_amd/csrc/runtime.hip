@@ -327,6 +327,7 @@ extern "C" int frido_sizeof_desc(int32_t kind) {
         case FRIDO_OP_ATTN_MH: return sizeof(FridoAttnMh);
         case FRIDO_DESC_KEEP_BLEND: return sizeof(FridoKeepBlend);
         case FRIDO_DESC_INVERT_STEP: return sizeof(FridoInvertStep);
+        case FRIDO_DESC_GUIDANCE_COMPOSE: return sizeof(FridoGuidanceCompose);
         default: return -1;
     }
 }

@@ -45,10 +45,18 @@ def all_gather_images(local, total=None, group=None):
     return torch.cat([out[r * bmax: r * bmax + (hi - lo)] for r, (lo, hi) in enumerate(sizes)], dim=0)
 
 
+def _guide_kw(compose, guidance_rescale):
+    """The samplers' composed-guidance keywords, passed only when one is in use: a call without them is the call it always was."""
+    return dict(compose=compose, guidance_rescale=guidance_rescale) if compose is not None or guidance_rescale else {}
+
+
 @torch.no_grad()
 def sample_images(model, cond, *, S, eta=1.0, sampler="ddim", scale=1.0, uncond=None, seed=0, sample0=0, noise="philox",
-                  num_stage=None, gather=True, total=None, log_every_t=10 ** 9, gather_dtype="float32", check_status=True):
+                  num_stage=None, gather=True, total=None, log_every_t=10 ** 9, gather_dtype="float32", check_status=True, compose=None,
+                  guidance_rescale=0.0):
     """cond: this rank's conditioning shard [b, nctx, cd] on the GPU.  Returns decoded images (gathered).
+    compose / guidance_rescale: composed guidance (the samplers' keywords; `scale` is the weight of `cond`); every conditioning of
+    `compose` is this rank's shard, cut like `cond` (shard_range).
     gather_dtype "float32": (N, 3, H, W) f32 in [-1, 1] (what decode_first_stage returns; 25 MB / rank at 32 images);
     "uint8" / "uint8_pil": the (N, H, W, 3) uint8 images of scripts/sample_diffusion.py custom_to_np (:115-121) / custom_to_pil
     (:103-113), produced by the decoder's last epilogue -- the one all-gather then moves 6.3 MB / rank.
@@ -58,11 +66,13 @@ def sample_images(model, cond, *, S, eta=1.0, sampler="ddim", scale=1.0, uncond=
     unet = model.model.diffusion_model
     b = cond.shape[0]
     shape = (unet.in_channels, unet.image_size, unet.image_size)
+    guide = _guide_kw(compose, guidance_rescale)
     if sampler == "ddpm":
         # the ancestral loop (FridoDiffusion.p_sample_loop): S = chain length (t = S - 1 ... 0 per stage); it has no guidance, its noise
         # level is the posterior's (what eta = 1 means to DDIM) and it always walks every stage of the model
-        if scale != 1.0 or uncond is not None:
-            raise ValueError("sampler='ddpm': the ancestral loop has no classifier-free guidance (scale must be 1.0, uncond None)")
+        if scale != 1.0 or uncond is not None or compose is not None or guidance_rescale:
+            raise ValueError("sampler='ddpm': the ancestral loop has no classifier-free guidance (scale must be 1.0, uncond None, no compose / "
+                             "guidance_rescale)")
         if eta != 1.0:
             raise ValueError(f"sampler='ddpm': the ancestral loop has no eta (got {eta}; leave it at 1.0)")
         if num_stage is not None and num_stage != model.num_resulotion:
@@ -77,12 +87,12 @@ def sample_images(model, cond, *, S, eta=1.0, sampler="ddim", scale=1.0, uncond=
         from .samplers import DPMSolverSampler
         z, _ = DPMSolverSampler(model).sample(S=S, batch_size=b, shape=shape, conditioning=cond, num_stage=num_stage or unet.num_stage,
                                               verbose=False, unconditional_guidance_scale=scale, unconditional_conditioning=uncond,
-                                              noise=noise, seed=seed, sample0=sample0, log_every_t=log_every_t)
+                                              noise=noise, seed=seed, sample0=sample0, log_every_t=log_every_t, **guide)
     else:
         cls = PLMSSampler if sampler == "plms" else DDIMSampler
         z, _ = cls(model).sample(S=S, batch_size=b, shape=shape, conditioning=cond, num_stage=num_stage or unet.num_stage,
                                  eta=eta, verbose=False, unconditional_guidance_scale=scale, unconditional_conditioning=uncond,
-                                 noise=noise, seed=seed, sample0=sample0, log_every_t=log_every_t)
+                                 noise=noise, seed=seed, sample0=sample0, log_every_t=log_every_t, **guide)
     if gather_dtype == "float32":
         img = model.decode_first_stage(z)
     elif gather_dtype in ("uint8", "uint8_pil"):
@@ -98,12 +108,12 @@ def sample_images(model, cond, *, S, eta=1.0, sampler="ddim", scale=1.0, uncond=
 @torch.no_grad()
 def edit_images(model, images, cond, *, S, strength, keep_mask=None, eta=1.0, scale=1.0, uncond=None, seed=0, sample0=0, noise="philox",
                 num_stage=None, init="z0", reimpose=True, gather=True, total=None, log_every_t=10 ** 9, gather_dtype="float32",
-                check_status=True):
+                check_status=True, compose=None, guidance_rescale=0.0):
     """Image-to-image / inpainting on this rank's shard: images (b, 3, H, W) in [-1, 1] on the GPU -> encode_first_stage +
     get_first_stage_encoding -> DDIMSampler.edit (the last clamp(int(strength * S), 1, S) of S steps per stage) -> decode_first_stage.
     keep_mask (b, 1, H, W) in [0, 1] over the PIXELS, 1 = keep: min-pooled to the latent grid (a latent cell is kept only if every pixel
     it decodes to is).  Noise is keyed by (seed, GLOBAL sample index = sample0 + i), so a sharded run equals the whole batch; gather /
-    gather_dtype / check_status as in sample_images."""
+    gather_dtype / check_status / compose / guidance_rescale as in sample_images."""
     from .samplers import DDIMSampler
     unet = model.model.diffusion_model
     z0 = model.get_first_stage_encoding(model.encode_first_stage(images))
@@ -115,7 +125,7 @@ def edit_images(model, images, cond, *, S, strength, keep_mask=None, eta=1.0, sc
         m = -torch.nn.functional.max_pool2d(-keep_mask.float(), f, f) if f > 1 else keep_mask.float()
     z, _ = DDIMSampler(model).edit(S, z0, cond, strength=strength, keep_mask=m, init=init, reimpose=reimpose, num_stage=num_stage or unet.num_stage,
                                    eta=eta, unconditional_guidance_scale=scale, unconditional_conditioning=uncond, noise=noise, seed=seed,
-                                   sample0=sample0, log_every_t=log_every_t, verbose=False)
+                                   sample0=sample0, log_every_t=log_every_t, verbose=False, **_guide_kw(compose, guidance_rescale))
     if gather_dtype == "float32":
         img = model.decode_first_stage(z)
     elif gather_dtype in ("uint8", "uint8_pil"):

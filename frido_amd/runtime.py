@@ -36,6 +36,9 @@ KEEP_BLEND = "keep_blend"
 FOREIGN[KEEP_BLEND] = "frido_keep_blend"  # op tag of the editing blend (csrc/edit.hip) in front of a model evaluation
 INVERT_STEP = "invert_step"
 FOREIGN[INVERT_STEP] = "frido_invert_step"  # op tag of the DDIM inversion update (csrc/invert.hip)
+GUIDANCE_COMPOSE = "guidance_compose"
+FOREIGN[GUIDANCE_COMPOSE] = "frido_guidance_compose"  # op tag of the composed-guidance step (csrc/guidance.hip) behind a model evaluation
+GUIDANCE_MAX = 8                          # conditionings per composed engine: the main one and up to 7 of `compose=`
 EDIT_RNG_STREAM = 64                      # Philox stream of stage s's blend draws: 64 + s, apart from 0 (x_T) and 1 .. num_stage (the updates)
 
 
@@ -274,7 +277,14 @@ class SamplerEngine:
     read a crop buffer, and every model evaluation is frido_unfold(x -> crops) -> step program -> frido_fold(crop eps -> full eps), all
     inside the captured step body (patching.PatchProg).  A stage's `pre` program reads the crop buffer too (the SPADE maps come from the
     frozen channels), so an unfold precedes it.  Memory: everything per-sample in the plans -- activations, the SPADE maps and the
-    cross-attention K / V^T caches (B * L * xrep rows) -- is L times the whole-latent engine's at the crop size."""
+    cross-attention K / V^T caches (B * L * xrep rows) -- is L times the whole-latent engine's at the crop size.
+
+    ncond / rescale: an engine is COMPOSED when ncond > 1 or rescale.  Its plans evaluate xrep = ncond + 1 conditionings per step --
+    [c_0 | ... | c_{ncond-1} | uncond] -- and every model evaluation is followed by frido_guidance_compose, which mixes them in place into
+    slot 0 with the device weights guide_w (w_0 .. w_{ncond-1}, then the rescale factor phi: run(weights=, phi=) fills them, so other values
+    replay the same graphs); the update kernel then reads slot 0 as an already mixed eps (the score corrector's route), whatever its kind.
+    Memory: everything per-sample in the plans -- activations, SPADE maps, K / V^T caches, a class-conditional denoiser's S * Bx embedding
+    table -- is (ncond + 1) / 2 times the classifier-free engine's.  A non-composed engine has none of this: same ops, buffers and graphs."""
 
     def __init__(self, builder: Builder, cfg, **kw):
         self.planes = builder.planes
@@ -283,13 +293,22 @@ class SamplerEngine:
 
     def _init(self, builder: Builder, cfg, *, B, C, H, W, nctx, S, eta, kind, alphas_cumprod, embed_dim, cfg_scale=1.0,
               use_graph=True, num_stage=None, temperature=1.0, posterior=None, clip=False, patch=None, order=2, skip_type="logSNR",
-              lower_order_final=True):
+              lower_order_final=True, ncond=1, rescale=False, compose_always=False):
         self.b, self.cfg = builder, cfg
         self.dev = builder.device
         self.B, self.C, self.H, self.W, self.nctx = B, C, H, W, nctx
         self.kind = kind
         self.cfg_scale = float(cfg_scale)
         self.xrep = 2 if self.cfg_scale != 1.0 else 1
+        self.ncond, self.rescale = int(ncond), bool(rescale)
+        # compose_always: one conditioning without rescale through the composed route all the same (tools/compose_step_bench.py measures
+        # the route's own cost with it; no public call sets it)
+        self.composed = self.ncond > 1 or self.rescale or bool(compose_always)
+        if self.composed:
+            assert 1 <= self.ncond <= GUIDANCE_MAX, f"1 to {GUIDANCE_MAX} conditionings, got {ncond}"
+            assert kind in ("ddim", "plms", "dpm") and patch is None, "composed guidance is built for the whole-latent DDIM / PLMS / DPM-Solver loops"
+            self.xrep = self.ncond + 1
+            self.guide_w = torch.zeros(self.ncond + 1, dtype=torch.float32, device=builder.device)      # the weights, then phi
         self.embed = list(embed_dim)
         self.num_stage = num_stage if num_stage is not None else cfg.get("num_stage", 1)
         self.use_graph = use_graph
@@ -396,8 +415,14 @@ class SamplerEngine:
         return p
 
     def _eval_ops(self, s):
-        """The ops of ONE model evaluation at stage s, leaving eps where _eps_ptr(s) points."""
+        """The ops of ONE model evaluation at stage s, leaving eps where _eps_ptr(s) points -- on a composed engine the guidance-mixed
+        eps, in slot 0 of the xrep evaluations."""
         plan = self.stages[s]
+        if self.composed:
+            eps = self._eps_ptr(s)
+            mix = _lib.STRUCTS["FridoGuidanceCompose"](eps=eps, out=eps, weights=self.guide_w.data_ptr(), n=self.ncond, B=self.B,
+                                                       per_sample=self.H * self.W * plan.nch, rescale=int(self.rescale))
+            return list(plan.step.ops) + [(GUIDANCE_COMPOSE, mix)]
         if self.geo is None:
             return list(plan.step.ops)
         from .patching import FOLD, UNFOLD
@@ -411,19 +436,20 @@ class SamplerEngine:
         """(op tag, descriptor) of stage s's state update on the engine's buffers, for its kind: the DDIM / PLMS step (hist_mode: how PLMS uses
         its eps ring), the ancestral step, or (DPM_STEP, FridoDpmStep) with the stage's x0 history.  noise: None -- Philox in the kernel, keyed
         by the device {seed, sample0} -- or (address, channels) of host noise [step][B][HW][channels] read by step index.  no_cfg: the eps is
-        already guidance-mixed (a score corrector ran)."""
+        already guidance-mixed (a score corrector ran); a composed engine's always is."""
         B, HW, C = self.B, self.H * self.W, self.C
         start, nch, eps = sum(self.embed[:s]), self.embed[s], self._eps_ptr(s)
+        cfg2 = not self.composed and self.xrep == 2      # the update kernel mixes [cond | uncond] itself
         if self.kind == "invert":       # (INVERT_STEP, FridoInvertStep): the stage's window only, no noise, no x0
             return INVERT_STEP, _lib.STRUCTS["FridoInvertStep"](
-                x=self.x.data_ptr(), eps_cond=eps, eps_uncond=eps + 4 * B * HW * nch if self.xrep == 2 else None, cfg_scale=self.cfg_scale,
+                x=self.x.data_ptr(), eps_cond=eps, eps_uncond=eps + 4 * B * HW * nch if cfg2 else None, cfg_scale=self.cfg_scale,
                 cfg_dev=self.cfg_dev.data_ptr(), coef=self.coef.data_ptr(), step=self.step.data_ptr(), B=B, HW=HW, Cx=C, c_lo=start,
                 c_hi=start + nch)
         kw = dict(x=self.x.data_ptr(), B=B, HW=HW, Cx=C, start=start, nch=nch, eps_cond=eps, coef=self.coef.data_ptr(),
                   step=self.step.data_ptr(), x_out=self.x.data_ptr(), pred_x0=self.pred_x0.data_ptr())
         if self.kind != "ddpm":
             kw.update(cfg_scale=self.cfg_scale, cfg_dev=self.cfg_dev.data_ptr())
-            if self.xrep == 2 and not no_cfg:
+            if cfg2 and not no_cfg:
                 kw["eps_uncond"] = eps + 4 * B * HW * nch
         if self.kind == "dpm":
             return DPM_STEP, _lib.STRUCTS["FridoDpmStep"](x0_hist=self.x0_hist[s].data_ptr(), **kw)
@@ -484,7 +510,13 @@ class SamplerEngine:
 
     def _context(self, cond, uncond=None):
         """cond on the device: the cross-attention context (SpatialTransformer denoisers), class labels (class-conditional ones) or None;
-        under classifier-free guidance [cond | uncond]."""
+        under classifier-free guidance [cond | uncond]; on a composed engine cond is the sequence (c_0, ..., c_{ncond-1}) and the result
+        [c_0 | ... | c_{ncond-1} | uncond]."""
+        if self.composed:
+            assert len(cond) == self.ncond and uncond is not None, "a composed engine takes its ncond conditionings and the unconditional one"
+            first = cond[0]
+            dt = torch.float32 if not self.labels or first.is_floating_point() else torch.int64
+            return torch.cat([c.to(self.dev, dt) for c in cond] + [uncond.to(self.dev, dt)], dim=0)
         ctx = cond.to(self.dev, torch.float32 if not self.labels or cond.is_floating_point() else torch.int64) if cond is not None else None
         if self.xrep == 2:
             assert ctx is not None, "classifier-free guidance needs a conditioning"
@@ -565,7 +597,8 @@ class SamplerEngine:
     @torch.no_grad()
     @_lib.with_planes
     def run(self, cond, uncond=None, *, x_T=None, noise="philox", seed=0, sample0=0, log_every_t=100, callback=None,
-            img_callback=None, noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, model=None, edit=None):
+            img_callback=None, noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, model=None, edit=None, weights=None,
+            phi=0.0):
         """Runs all stages.  noise: "philox" (device counter RNG), "torch" (draw from torch's global CPU generator in
         exactly the reference's order -- the stream of a reference run on CPU with the same torch.manual_seed), or a
         callable shape -> tensor replaying a recorded tape.  A supplied x_T is, like in the reference (ddim.py:150-152,
@@ -578,8 +611,14 @@ class SamplerEngine:
         edit (an EditSpec; kind "ddim", whole-latent engines): img2img / keep-mask inpainting, see _edit_stage.  Every stage from
         edit.first_stage on runs the LAST edit.k steps of the chain; the stages below it keep the start state's channels (no steps, no
         hand-off: what an adopted x_T gets), and x_T is only the start state of init="noise", it adopts nothing by itself.
+        weights / phi (a composed engine; cond is then the sequence of its ncond conditionings): this run's ncond guidance weights and its
+        rescale factor, written to the device vector the captured frido_guidance_compose launches read.
         Returns (samples NCHW, intermediates dict)."""
         assert self.kind != "ddpm", "an ancestral engine runs through run_ancestral()"
+        assert self.composed == (weights is not None), "weights= belongs to a composed engine, and a composed engine needs it"
+        if self.composed:
+            assert len(weights) == self.ncond and score_corrector is None, "ncond weights; a composed engine has no score_corrector hook"
+            assert self.rescale or phi == 0.0, "phi needs an engine built with rescale=True"
         assert self.kind != "invert", "an inversion engine runs through run_invert()"
         if edit is not None:
             assert self.kind == "ddim" and self.geo is None, "editing is built for the whole-latent DDIM engine"
@@ -601,6 +640,8 @@ class SamplerEngine:
         with own_stream(self, self.dev) as sp:
             ctx = self._context(cond, uncond)
             self.cfg_dev.fill_(self.cfg_scale)
+            if self.composed:
+                self.guide_w.copy_(torch.tensor([float(w) for w in weights] + [float(phi)], dtype=torch.float32))
             if edit is not None:
                 self._bind_edit(edit, sp)
             if edit is not None and edit.init == "z0":

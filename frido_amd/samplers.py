@@ -65,6 +65,57 @@ def edit_steps(S, t_start=None, strength=None):
     return int(t_start)
 
 
+COMPOSE_MAX = 7            # entries of `compose=`: with the main conditioning, the 8 slots of frido_guidance_compose
+
+
+def check_compose(who, model, conditioning, unconditional_conditioning, scale, compose, guidance_rescale, score_corrector=None):
+    """What `compose=` / `guidance_rescale=` ask before anything is planned.  Returns None for a call without them -- today's path -- or
+    (conditionings, weights, phi): the main conditioning first with weight `scale`, then the entries of `compose` in their order."""
+    if compose is None and isinstance(guidance_rescale, (int, float)) and guidance_rescale == 0:
+        return None
+    no = lambda what: NotImplementedError(f"{who}: {what} is not built for composed guidance (compose= / guidance_rescale=)")
+    from . import patching
+    if patching.params_of(model) is not None:
+        raise patching.refuse(f"{who}: composed guidance (compose= / guidance_rescale=)")
+    if score_corrector is not None:
+        raise no("score_corrector")
+    entries = list(compose) if compose is not None else []
+    if isinstance(compose, dict) or any(not isinstance(e, (tuple, list)) or len(e) != 2 for e in entries):
+        raise ValueError(f"{who}: compose is a sequence of (conditioning, weight) pairs")
+    if isinstance(conditioning, (dict, list)) or isinstance(unconditional_conditioning, (dict, list)) or \
+            any(isinstance(c, (dict, list)) for c, _ in entries):
+        raise no("a dict / list conditioning")
+    if isinstance(guidance_rescale, bool) or not isinstance(guidance_rescale, (int, float, np.integer, np.floating)) or \
+            not 0.0 <= float(guidance_rescale) <= 1.0:
+        raise ValueError(f"{who}: guidance_rescale={guidance_rescale!r} must be a number in [0, 1]")
+    if len(entries) > COMPOSE_MAX:
+        raise ValueError(f"{who}: compose holds {len(entries)} entries, at most {COMPOSE_MAX} fit beside the main conditioning")
+    if unconditional_conditioning is None or not torch.is_tensor(conditioning):
+        raise ValueError(f"{who}: compose= / guidance_rescale= need a conditioning and an unconditional_conditioning (every term is "
+                         "measured against the unconditional evaluation)")
+    for i, (c, w) in enumerate(entries):
+        if not torch.is_tensor(c) or c.shape != conditioning.shape or c.device != conditioning.device or \
+                c.is_floating_point() != conditioning.is_floating_point():
+            raise ValueError(f"{who}: compose[{i}] must be a tensor like conditioning ({tuple(conditioning.shape)}, "
+                             f"{'floating' if conditioning.is_floating_point() else 'integer'}, on {conditioning.device}), got "
+                             f"{(tuple(c.shape), c.dtype, str(c.device)) if torch.is_tensor(c) else type(c).__name__}")
+    weights = [scale] + [w for _, w in entries]
+    for i, w in enumerate(weights):
+        if isinstance(w, bool) or not isinstance(w, (int, float, np.integer, np.floating)) or not np.isfinite(float(w)):
+            raise ValueError(f"{who}: weight {w!r} of {'the main conditioning' if i == 0 else f'compose[{i - 1}]'} must be a finite real number")
+    if not entries and float(guidance_rescale) == 0.0:
+        return None         # an empty composition without rescale is classifier-free guidance: today's path
+    return [conditioning] + [c for c, _ in entries], [float(w) for w in weights], float(guidance_rescale)
+
+
+def _composed_call(comp, conditioning):
+    """check_compose's result -> (what SamplerEngine.run takes as cond, the engine key's (ncond, rescale on) or None, run's extra keywords)."""
+    if comp is None:
+        return conditioning, None, {}
+    conds, weights, phi = comp
+    return conds, (len(conds), phi != 0.0), dict(weights=weights, phi=phi)
+
+
 class _SamplerBase:
     KIND = "ddim"
 
@@ -88,24 +139,40 @@ class _SamplerBase:
         self.ddim_sqrt_one_minus_alphas = np.sqrt((np.float32(1.0) - al).astype(np.float32))
         self.alphas_cumprod = ac
 
-    def _engine(self, B, shape, nctx, S, eta, scale, num_stage, temperature, replica=0, patch=None, solver=None, kind=None):
+    def _engine_key(self, B, shape, nctx, S, eta, scale, num_stage, temperature, replica=0, patch=None, solver=None, kind=None, composed=None):
+        """The engine-cache key of a call (no device is touched).  composed: None, or (ncond, rescale on) of a call with compose= /
+        guidance_rescale= -- appended only then, the way `patch` extends the key: a call without the keywords finds the engine it always
+        found.  The weights and the rescale factor are device state, not part of the key."""
+        C, H, W = shape
+        guided = scale != 1.0 or composed is not None      # a composed engine's scale is one of its weights: every scale shares it
+        if solver is None:
+            key = (kind or self.KIND, B, C, H, W, nctx, S, float(eta), guided, num_stage, float(temperature), replica)
+        else:
+            key = (self.KIND, B, C, H, W, nctx, S, guided, num_stage, replica) + solver
+        if patch is not None:      # patch-wise mode (model.split_input_params): plans, buffers and graphs of its own
+            from .patching import geometry_key
+            key += (geometry_key(patch),)
+        if composed is not None:
+            key += (("compose",) + tuple(composed),)
+        return key
+
+    def _engine(self, B, shape, nctx, S, eta, scale, num_stage, temperature, replica=0, patch=None, solver=None, kind=None, composed=None):
         """The cached SamplerEngine of this call.  solver: DPM-Solver++'s (order, skip_type, lower_order_final), part of its engine's key where
         DDIM / PLMS have eta and the temperature; its table is computed from the float64 schedule.  kind: another loop of this sampler
-        ("invert": DDIMSampler.invert), with engines -- plans, tables, graphs -- of its own under its own key."""
+        ("invert": DDIMSampler.invert), with engines -- plans, tables, graphs -- of its own under its own key.  composed: (ncond, rescale on)
+        of a call with compose= / guidance_rescale=, an engine of its own (SamplerEngine(ncond=, rescale=))."""
         kind = kind or self.KIND
         from .runtime import SamplerEngine
         unet = self.model.model.diffusion_model
         rt = unet.runtime()
         C, H, W = shape
+        key = self._engine_key(B, shape, nctx, S, eta, scale, num_stage, temperature, replica, patch, solver, kind, composed)
         if solver is None:
-            key = (kind, B, C, H, W, nctx, S, float(eta), scale != 1.0, num_stage, float(temperature), replica)
             more, ac = dict(temperature=temperature, patch=patch), self.model.alphas_cumprod.detach().float()
         else:
-            key = (self.KIND, B, C, H, W, nctx, S, scale != 1.0, num_stage, replica) + solver
             more, ac = dict(zip(("order", "skip_type", "lower_order_final"), solver)), self.model.alphas_cumprod.detach().double()
-        if patch is not None:      # patch-wise mode (model.split_input_params): plans, buffers and graphs of its own
-            from .patching import geometry_key
-            key += (geometry_key(patch),)
+        if composed is not None:
+            more.update(ncond=composed[0], rescale=composed[1])
         eng = cached_engine(rt, key, lambda: SamplerEngine(
             rt.builder_for(replica), unet.cfg, B=B, C=C, H=H, W=W, nctx=nctx if isinstance(nctx, int) else 0, S=S, eta=eta, kind=kind,
             alphas_cumprod=ac.cpu().numpy(), embed_dim=self.model.embed_dim_list, cfg_scale=scale, num_stage=num_stage, **more))
@@ -133,7 +200,11 @@ class _SamplerBase:
                img_callback=None, quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0.,
                score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
                unconditional_guidance_scale=1., unconditional_conditioning=None, noise="torch", seed=0, sample0=0,
-               replica=0, **kwargs):
+               replica=0, compose=None, guidance_rescale=0., **kwargs):
+        """compose (a sequence of up to 7 (conditioning_i, weight_i)) / guidance_rescale (phi in [0, 1]): composed guidance, see
+        check_compose and SamplerEngine -- eps = e_u + s (e_c - e_u) + sum_i w_i (e_i - e_u) with s = unconditional_guidance_scale the
+        weight of `conditioning`, terms added in that order, then (phi > 0) scaled per sample by phi sigma(e_c) / sigma(eps) + 1 - phi.
+        Both need unconditional_conditioning; split_input_params, score_corrector and dict / list conditionings are refused by name."""
         if mask is not None or x0 is not None:
             # ddim.py:158-161 / plms.py blend `q_sample(x0, ts) * mask + (1 - mask) * img`, but img carries only the channels of the
             # stages reached so far: with num_stage > 1 -- every Frido model -- the reference itself raises a RuntimeError (size
@@ -144,6 +215,8 @@ class _SamplerBase:
             raise NotImplementedError("quantize_x0: the reference calls exit() on this option (ddim.py:251-253)")
         # patch-wise mode (frido.py:1076-1152): the samplers inherit it from apply_model; looked up on every call, like the reference's hasattr
         from . import patching
+        comp = check_compose(f"{type(self).__name__}.sample", self.model, conditioning, unconditional_conditioning,
+                             unconditional_guidance_scale, compose, guidance_rescale, score_corrector)
         patch = patching.params_of(self.model)
         if patch is not None:
             if score_corrector is not None:
@@ -158,15 +231,16 @@ class _SamplerBase:
         if verbose:
             print(f"Data shape for {self.KIND.upper()} sampling is {(batch_size, *shape)}, eta {eta}")
         self.num_stage = num_stage
+        conds, composed, guide = _composed_call(comp, conditioning)
 
         def go(noise_src):
             # the engine is looked up per attempt: a repeated run (autoplanes: the default plane format saturated) belongs to the
             # denoiser's NEW runtime on the bf16-pair build, with its own plans, buffers and graphs
             eng = self._engine(batch_size, tuple(shape), mode, S, eta, unconditional_guidance_scale, num_stage,
-                               temperature, replica, patch)
-            return eng.run(conditioning, unconditional_conditioning, x_T=x_T, noise=noise_src, seed=seed, sample0=sample0,
+                               temperature, replica, patch, composed=composed)
+            return eng.run(conds, unconditional_conditioning, x_T=x_T, noise=noise_src, seed=seed, sample0=sample0,
                            log_every_t=log_every_t, callback=callback, img_callback=img_callback, noise_dropout=noise_dropout,
-                           score_corrector=score_corrector, corrector_kwargs=corrector_kwargs, model=self.model)
+                           score_corrector=score_corrector, corrector_kwargs=corrector_kwargs, model=self.model, **guide)
         from . import autoplanes
         return autoplanes.run(self.model.model.diffusion_model, go, f"{type(self).__name__}.sample", noise=noise)
 
@@ -174,7 +248,7 @@ class _SamplerBase:
     def edit(self, S, z0, conditioning=None, *, t_start=None, strength=None, keep_mask=None, init="z0", blend="stage", reimpose=True,
              first_stage=0, num_stage=1, eta=0., x_T=None, temperature=1., unconditional_guidance_scale=1.,
              unconditional_conditioning=None, noise="torch", seed=0, sample0=0, callback=None, img_callback=None, log_every_t=100,
-             verbose=True, replica=0, score_corrector=None, noise_dropout=0.):
+             verbose=True, replica=0, score_corrector=None, noise_dropout=0., compose=None, guidance_rescale=0.):
         """Edit the latent z0 (B, C, H, W) instead of sampling one: the LAST k of the S DDIM steps in every stage from `first_stage` on,
         k = t_start or clamp(int(strength * S), 1, S).  Returns (samples, intermediates) like `sample`.  (Where S does not divide the model's
         timesteps the uniform grid has more than S rows -- 7 at S = 6 of 1000 -- and k still counts from its end.)
@@ -193,6 +267,7 @@ class _SamplerBase:
         Stages below first_stage keep the start state's channels (z0's, or x_T's under init="noise").
         noise: "torch" / a tape draw per stage in the reference's order -- the start draw, then per step the blend's draw and the update's
         draw, each (B, e_s, H, W); "philox": keyed by (seed, global sample index), the blend draws on streams of their own.
+        compose / guidance_rescale: composed guidance, as in `sample`.
         `sample(mask=, x0=)` stays refused; PLMS / DPM-Solver editing, split_input_params, score_corrector, noise_dropout and dict / list
         conditionings are refused by name."""
         no = lambda what: NotImplementedError(f"{type(self).__name__}.edit: {what} is not built for editing")
@@ -207,6 +282,8 @@ class _SamplerBase:
             raise no("noise_dropout")
         if isinstance(conditioning, (dict, list)) or isinstance(unconditional_conditioning, (dict, list)):
             raise no("a dict / list conditioning")
+        comp = check_compose(f"{type(self).__name__}.edit", self.model, conditioning, unconditional_conditioning,
+                             unconditional_guidance_scale, compose, guidance_rescale)
         k = edit_steps(S, t_start, strength)
         if init not in ("z0", "noise") or blend not in ("stage", "reference"):
             raise ValueError(f"edit: init={init!r} ('z0' or 'noise'), blend={blend!r} ('stage' or 'reference')")
@@ -238,18 +315,19 @@ class _SamplerBase:
         from .runtime import EditSpec, stage_masks
         masks = stage_masks(keep_mask.float(), num_stage) if keep_mask is not None else None
         spec = EditSpec(z0, k, self.model.sqrt_alphas_cumprod, self.model.sqrt_one_minus_alphas_cumprod, masks, init, blend, reimpose, first_stage)
+        conds, composed, guide = _composed_call(comp, conditioning)
 
         def go(noise_src):
-            eng = self._engine(B, shape, mode, S, eta, unconditional_guidance_scale, num_stage, temperature, replica)
-            return eng.run(conditioning, unconditional_conditioning, x_T=x_T, noise=noise_src, seed=seed, sample0=sample0,
-                           log_every_t=log_every_t, callback=callback, img_callback=img_callback, model=self.model, edit=spec)
+            eng = self._engine(B, shape, mode, S, eta, unconditional_guidance_scale, num_stage, temperature, replica, composed=composed)
+            return eng.run(conds, unconditional_conditioning, x_T=x_T, noise=noise_src, seed=seed, sample0=sample0,
+                           log_every_t=log_every_t, callback=callback, img_callback=img_callback, model=self.model, edit=spec, **guide)
         from . import autoplanes
         return autoplanes.run(self.model.model.diffusion_model, go, f"{type(self).__name__}.edit", noise=noise)
 
     @torch.no_grad()
     def invert(self, S, z0, conditioning=None, *, t_start=None, strength=None, first_stage=0, num_stage=1,
                unconditional_guidance_scale=1., unconditional_conditioning=None, log_every_t=100, callback=None, verbose=True, replica=0,
-               score_corrector=None):
+               score_corrector=None, compose=None, guidance_rescale=0.):
         """DDIM inversion (DDIM's deterministic encoder; upstream latent-diffusion's DDIMSampler.encode, not in the reference): walk the
         probability-flow ODE UPWARDS from the clean latent z0 (B, C, H, W) through the first k rows of the S-step grid,
         k = t_start or clamp(int(strength * S), 1, S) -- the rows `edit` counts from the chain's end.  Row i, evaluated at
@@ -260,8 +338,11 @@ class _SamplerBase:
         below first_stage and every other window at level ddim_alphas[k - 1], where
         `edit(S, z0, c, init="noise", x_T=x_inv, t_start=k, first_stage=f, eta=0)` starts -- with the same conditioning it comes back to
         z0 up to the discretisation error, with another one it edits.  Deterministic: no generator is touched.
-        PLMS / DPM-Solver inversion, split_input_params, score_corrector and dict / list conditionings are refused by name."""
+        PLMS / DPM-Solver inversion, split_input_params, score_corrector, composed guidance (compose= / guidance_rescale=) and dict / list
+        conditionings are refused by name."""
         no = lambda what: NotImplementedError(f"{type(self).__name__}.invert: {what} is not built for inversion")
+        if compose is not None or guidance_rescale:
+            raise no("composed guidance (compose= / guidance_rescale=)")
         if self.KIND != "ddim":
             raise no(f"{type(self).__name__} (inversion walks DDIM's chain: use DDIMSampler.invert)")
         from . import patching
@@ -325,7 +406,7 @@ class DPMSolverSampler(_SamplerBase):
                img_callback=None, quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0.,
                score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
                unconditional_guidance_scale=1., unconditional_conditioning=None, noise="torch", seed=0, sample0=0,
-               replica=0, order=2, skip_type="logSNR", lower_order_final=True, **kwargs):
+               replica=0, order=2, skip_type="logSNR", lower_order_final=True, compose=None, guidance_rescale=0., **kwargs):
         no = lambda what, why: NotImplementedError(f"DPMSolverSampler: {what} -- {why}")
         if eta != 0:
             raise no(f"eta={eta}", "the multistep solver integrates the probability-flow ODE; it has no stochastic (SDE) variant here")
@@ -344,6 +425,8 @@ class DPMSolverSampler(_SamplerBase):
             raise patching.refuse("DPMSolverSampler")
         if isinstance(conditioning, (dict, list)) or isinstance(unconditional_conditioning, (dict, list)):
             raise no("dict / list conditionings", "pass the cross-attention conditioning tensor or the class labels")
+        comp = check_compose("DPMSolverSampler.sample", self.model, conditioning, unconditional_conditioning, unconditional_guidance_scale,
+                             compose, guidance_rescale)
         if order not in (1, 2):
             raise ValueError(f"DPMSolverSampler: order={order!r}, the multistep solver is built for order 1 and 2")
         if skip_type not in schedules.DPM_SKIP_TYPES:
@@ -357,10 +440,12 @@ class DPMSolverSampler(_SamplerBase):
             print(f"Data shape for DPM-Solver++ sampling is {(batch_size, *shape)}, order {order}, {skip_type} grid of {len(self.timesteps)} steps")
         self.num_stage = num_stage
         solver = (int(order), skip_type, bool(lower_order_final))
+        conds, composed, guide = _composed_call(comp, conditioning)
 
         def go(noise_src):
-            eng = self._engine(batch_size, tuple(shape), mode, S, 0.0, unconditional_guidance_scale, num_stage, 1.0, replica, solver=solver)
-            return eng.run(conditioning, unconditional_conditioning, x_T=x_T, noise=noise_src, seed=seed, sample0=sample0,
-                           log_every_t=log_every_t, callback=callback, img_callback=img_callback, model=self.model)
+            eng = self._engine(batch_size, tuple(shape), mode, S, 0.0, unconditional_guidance_scale, num_stage, 1.0, replica, solver=solver,
+                               composed=composed)
+            return eng.run(conds, unconditional_conditioning, x_T=x_T, noise=noise_src, seed=seed, sample0=sample0,
+                           log_every_t=log_every_t, callback=callback, img_callback=img_callback, model=self.model, **guide)
         from . import autoplanes
         return autoplanes.run(self.model.model.diffusion_model, go, f"{type(self).__name__}.sample", noise=noise)

@@ -573,6 +573,30 @@ typedef struct FridoInvertStep {
 } FridoInvertStep;
 #define FRIDO_DESC_INVERT_STEP 1002
 
+/* ---- composed guidance: several weighted conditionings against one unconditional evaluation (Liu et al. 2022, "Compositional Visual
+ * Generation with Composable Diffusion Models"; a negative weight negates) and the guidance rescale of Lin et al. 2024, not in the
+ * reference ----
+ * Not an op kind: an exported launcher with a descriptor of its own (frido_guidance_compose below), run eagerly or between
+ * frido_capture_begin and frido_capture_end.  eps holds n + 1 slots of B * per_sample floats: slot i < n the denoiser's output under
+ * conditioning i, slot n the unconditional one (the [cond | uncond] batch layout of the sampling engine for n = 1).  weights points to
+ * n + 1 DEVICE floats, w_0 .. w_{n-1} then phi, read by the kernel (other weights replay the same graph).  Per element in fp32, every
+ * product and sum rounded on its own (no contraction):
+ *   acc = e_u;   for i = 0 .. n - 1, in this order:   acc = acc + w_i (e_i - e_u)      (n = 1: FridoSamplerStep's expression, bit for bit)
+ *   rescale == 0:   out = acc                                                           (phi is not read)
+ *   rescale != 0:   out = acc * f_b,   f_b = phi * sigma(e_0) / sigma(acc) + (1 - phi)  per sample b over its per_sample elements
+ * sigma: the standard deviation, from float64 sums and sums of squares of the fp32 values added in a fixed order (no atomics: the same
+ * bits on every launch, whatever the alignment); f_b is formed in float64 and rounded once to fp32; sigma(acc) == 0 gives f_b = 1.
+ * out [B * per_sample] may BE slot 0 (the engine composes in place) and must not overlap the slots otherwise; the other slots are only
+ * read.  n in [1, 8].  rescale == 0 with B * per_sample a multiple of 4 and both bases 16-byte aligned: 16-byte accesses; scalar accesses
+ * otherwise.  rescale != 0: one workgroup per sample.  A non-finite out raises FRIDO_STATUS_NONFINITE. */
+typedef struct FridoGuidanceCompose {
+    const float* eps;            /* [n + 1][B * per_sample], the unconditional slot last */
+    float* out;                  /* [B * per_sample] */
+    const float* weights;        /* device: w_0 .. w_{n-1}, phi */
+    int32_t n, B, per_sample, rescale;
+} FridoGuidanceCompose;
+#define FRIDO_DESC_GUIDANCE_COMPOSE 1003
+
 enum FridoOpKind {
     FRIDO_OP_GEMM = 1, FRIDO_OP_GN_STATS, FRIDO_OP_GN_APPLY, FRIDO_OP_LAYERNORM, FRIDO_OP_SOFTMAX,
     FRIDO_OP_GEGLU, FRIDO_OP_PACK, FRIDO_OP_RELAYOUT, FRIDO_OP_VQ, FRIDO_OP_SAMPLER_STEP,
@@ -675,6 +699,9 @@ int frido_keep_blend(const FridoKeepBlend* d, frido_stream_t s);
 /* ---- the DDIM inversion update (descriptor above); bad arguments return FRIDO_EINVAL before any device is touched ---- */
 int frido_invert_step(const FridoInvertStep* d, frido_stream_t s);
 
+/* ---- composed guidance (descriptor above); bad arguments return FRIDO_EINVAL before any device is touched ---- */
+int frido_guidance_compose(const FridoGuidanceCompose* d, frido_stream_t s);
+
 /* ---- timing on the launch stream (HIP events) ---- */
 int frido_event_create(void** ev);
 int frido_event_record(void* ev, frido_stream_t s);
@@ -691,7 +718,8 @@ int frido_abi_version(void);
  * A host that packs weights / operands itself (hi = round(v), lo = round(v - hi) in this format) asks here. */
 int frido_x3_plane_format(void);
 int frido_sizeof_op(void);             /* sizeof(FridoOp): checked by the ctypes mirror */
-int frido_sizeof_desc(int32_t kind);   /* sizeof of the descriptor struct of that op kind (or of FRIDO_DESC_KEEP_BLEND / FRIDO_DESC_INVERT_STEP) */
+int frido_sizeof_desc(int32_t kind);   /* sizeof of the descriptor struct of that op kind (or of FRIDO_DESC_KEEP_BLEND / FRIDO_DESC_INVERT_STEP /
+                                          FRIDO_DESC_GUIDANCE_COMPOSE) */
 const char* frido_last_error(void);
 /* Sticky numerics status of the CURRENT device (r05): kernels cannot return errors, so operand producers and normalisation kernels
  * OR bits into a device word when they meet a value the arithmetic cannot represent, and this call reads it back (it synchronises
