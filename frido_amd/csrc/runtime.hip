@@ -12,6 +12,8 @@
 
 #include "common.h"
 
+static_assert(sizeof(FridoOp) == 520, "every descriptor fits the 512-byte union: a larger one changes the ABI of every program");
+
 namespace {
 thread_local char g_err[512] = "";
 }
@@ -61,6 +63,15 @@ int run_one(const FridoOp& op, frido_stream_t s) {
         case FRIDO_OP_ATTN_FLASH: return frido_attn_flash(&op.u.attn_small, s);
         case FRIDO_OP_L2NORM: return frido_l2norm(&op.u.l2norm, s);
         case FRIDO_OP_ATTN_MH: return frido_attn_mh(&op.u.attn_mh, s);
+        case FRIDO_OP_UNFOLD: return frido_unfold(&op.u.unfold, s);
+        case FRIDO_OP_FOLD: return frido_fold(&op.u.fold, s);
+        case FRIDO_OP_QSAMPLE: return frido_qsample(&op.u.qsample, s);
+        case FRIDO_OP_DIFFUSION_LOSS: return frido_diffusion_loss(&op.u.diffusion_loss, s);
+        case FRIDO_OP_VQ_COMMIT_LOSS: return frido_vq_commit_loss(&op.u.vq_commit_loss, s);
+        case FRIDO_OP_DPM_STEP: return frido_dpm_step(&op.u.dpm_step, s);
+        case FRIDO_OP_KEEP_BLEND: return frido_keep_blend(&op.u.keep_blend, s);
+        case FRIDO_OP_INVERT_STEP: return frido_invert_step(&op.u.invert_step, s);
+        case FRIDO_OP_GUIDANCE_COMPOSE: return frido_guidance_compose(&op.u.guidance_compose, s);
         default:
             frido_set_error("frido_run: unknown op kind %d", op.kind);
             return FRIDO_EINVAL;
@@ -325,9 +336,15 @@ extern "C" int frido_sizeof_desc(int32_t kind) {
         case FRIDO_OP_SYNC: return sizeof(FridoSync);
         case FRIDO_OP_L2NORM: return sizeof(FridoL2Norm);
         case FRIDO_OP_ATTN_MH: return sizeof(FridoAttnMh);
-        case FRIDO_DESC_KEEP_BLEND: return sizeof(FridoKeepBlend);
-        case FRIDO_DESC_INVERT_STEP: return sizeof(FridoInvertStep);
-        case FRIDO_DESC_GUIDANCE_COMPOSE: return sizeof(FridoGuidanceCompose);
+        case FRIDO_OP_UNFOLD: return sizeof(FridoUnfold);
+        case FRIDO_OP_FOLD: return sizeof(FridoFold);
+        case FRIDO_OP_QSAMPLE: return sizeof(FridoQSample);
+        case FRIDO_OP_DIFFUSION_LOSS: return sizeof(FridoDiffusionLoss);
+        case FRIDO_OP_VQ_COMMIT_LOSS: return sizeof(FridoVqCommitLoss);
+        case FRIDO_OP_DPM_STEP: return sizeof(FridoDpmStep);
+        case FRIDO_OP_KEEP_BLEND: return sizeof(FridoKeepBlend);
+        case FRIDO_OP_INVERT_STEP: return sizeof(FridoInvertStep);
+        case FRIDO_OP_GUIDANCE_COMPOSE: return sizeof(FridoGuidanceCompose);
         default: return -1;
     }
 }

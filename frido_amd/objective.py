@@ -17,13 +17,10 @@ import torch
 
 from . import _lib
 from .builder import Builder
-from .engine import lru_entry, own_stream
-from .patching import FOREIGN, PatchProg
+from .engine import Prog, lru_entry, own_stream
 from .runtime import _relayout
 from .unet_plan import UNetStagePlan
 
-QSAMPLE, LOSS = "qsample", "diffusion_loss"
-FOREIGN.update({QSAMPLE: "frido_qsample", LOSS: "frido_diffusion_loss"})
 LOSS_TYPES = {"l1": 0, "l2": 1}
 
 
@@ -38,7 +35,7 @@ def launch_loss(desc, stream):
 class LossEngine:
     """The plans, the state and the results of one (B, H, W, context length, precision).  What the plans do not depend on is given per
     call: the schedule tables and logvar are copied into device state, the objective's scalars (loss type, noise_mix_ratio, the two
-    weights) are descriptor fields of the two launchers and the stages to run select the launches -- so they key the captured graphs
+    weights) are descriptor fields of the two ops and the stages to run select the launches -- so they key the captured graphs
     (a handful of launches to record again), not the engine (two whole stage plans)."""
     GRAPHS = 8      # captured graphs kept per engine, least recently used first out
 
@@ -115,11 +112,12 @@ class LossEngine:
 
     def program(self, tape, stages, sc):
         """The whole call as one program: per stage of `stages` q_sample, the plan's two programs, the loss."""
-        prog = PatchProg(self.dev, self.b.nsplit)
+        prog = Prog(self.dev, self.b.nsplit)
         for s in stages:
             plan = self.stages[s]
             q, ls = self._descs(s, tape, sc)
-            prog.ops += [(QSAMPLE, q)] + list(plan.pre.ops) + list(plan.step.ops) + [(LOSS, ls)]
+            prog.ops += ([_lib.op_of("FRIDO_OP_QSAMPLE", q)] + list(plan.pre.ops) + list(plan.step.ops)
+                         + [_lib.op_of("FRIDO_OP_DIFFUSION_LOSS", ls)])
         prog.keep = list(self.stages)
         return prog
 

@@ -4,7 +4,7 @@ decode_first_stage, :963-993 encode_first_stage).
 
 The tensor is cut into overlapping crops (frido_unfold), the model runs on all crops as ONE batch, and the results are stitched with
 a border-distance weighting and divided by the folded weighting (frido_fold).  This module owns the geometry: the crop grid, the
-`weighting` / `normalization` tables (torch float32 on the host, once per geometry, bit-equal to the reference's tensors, uploaded), the descriptors of the two kernels, and a program type whose op list may contain them.
+`weighting` / `normalization` tables (torch float32 on the host, once per geometry, bit-equal to the reference's tensors, uploaded) and the descriptors of the two kernels (op kinds FRIDO_OP_UNFOLD / FRIDO_OP_FOLD).
 
 Batch layout of the crop tensor (include/frido_hip.h): crop l of sample b is entry b * L + l, so per-sample inputs of the model
 (timesteps, context, labels) are repeated with `repeat_interleave(L)`.
@@ -14,7 +14,6 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .engine import Graph, Prog
 
 MODEL, DECODE, ENCODE = "model", "decode", "encode"
 PARAM_KEYS = ("ks", "stride", "vqf", "patch_distributed_vq", "tie_braker", "clip_min_weight", "clip_max_weight", "clip_min_tie_weight",
@@ -175,64 +174,3 @@ def geometry_key(params):
     return (tuple(int(v) for v in params["ks"]), tuple(int(v) for v in params["stride"]), bool(params["tie_braker"]),
             float(params["clip_min_weight"]), float(params["clip_max_weight"]), float(params["clip_min_tie_weight"]),
             float(params["clip_max_tie_weight"]))
-
-
-# ---- a program whose op list may contain the two kernels ------------------------------------------------------------------------------
-UNFOLD, FOLD = "unfold", "fold"
-FOREIGN = {UNFOLD: "frido_unfold", FOLD: "frido_fold"}      # op tag -> exported launcher taking (descriptor, stream); frido_amd/objective.py adds its two
-
-
-class PatchProg(Prog):
-    """Prog whose `ops` may also hold (UNFOLD, FridoUnfold) / (FOLD, FridoFold) entries -- any (tag, descriptor) of FOREIGN.  run(): the descriptor ops in between go
-    through frido_run, segment by segment, in order on the stream; capture(): the same sequence between frido_capture_begin and
-    frido_capture_end -- one graph, replayed with frido_graph_launch like any other."""
-
-    def packed(self):
-        if self._packed is None:
-            segs, cur = [], []
-            for op in self.ops:
-                if op[0] in FOREIGN:
-                    if cur:
-                        segs.append(("ops", _lib.pack_ops(cur), len(cur)))
-                        cur = []
-                    segs.append((op[0], op[1], 1))
-                else:
-                    cur.append(op)
-            if cur:
-                segs.append(("ops", _lib.pack_ops(cur), len(cur)))
-            self._packed = segs
-        return self._packed
-
-    def _launch_all(self, stream):
-        L = _lib.lib()
-        for kind, what, n in self.packed():
-            if kind in FOREIGN:
-                name = FOREIGN[kind]
-                rc = getattr(L, name)(C.byref(what), stream)
-            else:
-                rc, name = L.frido_run(C.addressof(what), n, stream), "frido_run"
-            if rc != 0:
-                return rc, name
-        return 0, ""
-
-    def run(self, stream):
-        rc, name = self._launch_all(stream)
-        _lib.check(rc, name)
-
-    def run_timed(self, stream):
-        raise NotImplementedError("per-op timing of a patch-wise program: time its parts (tools/patch_step_bench.py)")
-
-    def capture(self, stream):
-        L = _lib.lib()
-        segs = self.packed()
-        _lib.check(L.frido_capture_begin(stream), "frido_capture_begin")
-        rc, name = self._launch_all(stream)
-        msg = L.frido_last_error().decode() if rc != 0 else ""
-        h = C.c_void_p()
-        rc_end = L.frido_capture_end(stream, C.byref(h))      # always: a failed body still has to end its capture
-        if rc != 0:
-            if rc_end == 0:
-                L.frido_graph_destroy(h)
-            raise _lib.FridoHipError(f"{name} failed inside a capture (rc={rc}): {msg}")
-        _lib.check(rc_end, "frido_capture_end")
-        return Graph(h, (segs, self))

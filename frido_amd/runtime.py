@@ -21,7 +21,6 @@ import torch
 from . import _lib, config
 from .builder import Builder
 from .engine import Prog, current_stream_ptr, own_stream, require_gpu
-from .patching import FOREIGN, PatchProg
 from .schedules import (ancestral_table, ddim_inversion_table, dpm_solver_table, make_ddim_sampling_parameters, make_ddim_timesteps,
                         sampler_coef_table)
 from .unet_plan import UNetStagePlan
@@ -30,14 +29,6 @@ from .vqgan_plan import VQDecodePlan, VQDecodeQuantPlan, VQEncodePlan
 # step bodies per captured DDIM graph (1 = one graph launch per step, the r01-r05 form; r06 default 20: 10 measured +0.17 %, 40 +0.28 % end to end, interleaved,
 # profiles/r06_graph_steps_ab.txt); see SamplerEngine._replay
 GRAPH_STEPS = max(1, int(os.environ.get("FRIDO_GRAPH_STEPS", "20")))
-DPM_STEP = "dpm_step"
-FOREIGN[DPM_STEP] = "frido_dpm_step"      # op tag of the DPM-Solver++ update inside a step body (patching.PatchProg)
-KEEP_BLEND = "keep_blend"
-FOREIGN[KEEP_BLEND] = "frido_keep_blend"  # op tag of the editing blend (csrc/edit.hip) in front of a model evaluation
-INVERT_STEP = "invert_step"
-FOREIGN[INVERT_STEP] = "frido_invert_step"  # op tag of the DDIM inversion update (csrc/invert.hip)
-GUIDANCE_COMPOSE = "guidance_compose"
-FOREIGN[GUIDANCE_COMPOSE] = "frido_guidance_compose"  # op tag of the composed-guidance step (csrc/guidance.hip) behind a model evaluation
 GUIDANCE_MAX = 8                          # conditionings per composed engine: the main one and up to 7 of `compose=`
 EDIT_RNG_STREAM = 64                      # Philox stream of stage s's blend draws: 64 + s, apart from 0 (x_T) and 1 .. num_stage (the updates)
 
@@ -275,7 +266,7 @@ class SamplerEngine:
     patch (a split_input_params dict; DDIM / PLMS only): the patch-wise mode of frido.py:1076-1152.  The state x, pred_x0, the PLMS eps
     ring, the stage hand-off and the update kernel stay on the FULL latent; the stage plans are built for the B * L crops (kh x kw) and
     read a crop buffer, and every model evaluation is frido_unfold(x -> crops) -> step program -> frido_fold(crop eps -> full eps), all
-    inside the captured step body (patching.PatchProg).  A stage's `pre` program reads the crop buffer too (the SPADE maps come from the
+    inside the captured step body.  A stage's `pre` program reads the crop buffer too (the SPADE maps come from the
     frozen channels), so an unfold precedes it.  Memory: everything per-sample in the plans -- activations, the SPADE maps and the
     cross-attention K / V^T caches (B * L * xrep rows) -- is L times the whole-latent engine's at the crop size.
 
@@ -398,18 +389,14 @@ class SamplerEngine:
             prog.emit("FRIDO_OP_STEP_ADD", step=self.step_bx.data_ptr(), delta=delta * self.Bm * self.xrep)
 
     def _prog(self, ops=()):
-        """A program for a step body -- in patch mode one whose op list may hold the unfold / fold launches, for the DPM solver one that may
-        hold its update (an exported launcher too, not an op kind) -- filled from `ops`: a (tag, descriptor) pair is one op, a list holds
-        finished ops (a model evaluation: _eval_ops), an int advances the step counter."""
-        foreign = any(not isinstance(o, int) and o[0] in FOREIGN for op in ops for o in (op if isinstance(op, list) else [op]))
-        p = PatchProg(self.dev, self.b.nsplit) if self.geo is not None or foreign else Prog(self.dev, self.b.nsplit)
+        """A program for a step body, filled from `ops`: a (kind name, fields) pair is one op, a list holds finished ops (a model
+        evaluation: _eval_ops), an int advances the step counter."""
+        p = Prog(self.dev, self.b.nsplit)
         for op in ops:
             if isinstance(op, int):
                 self._step_add(p, op)
             elif isinstance(op, list):
                 p.ops += op
-            elif op[0] in FOREIGN:
-                p.ops.append(op)
             else:
                 p.emit(op[0], **op[1])
         return p
@@ -420,28 +407,27 @@ class SamplerEngine:
         plan = self.stages[s]
         if self.composed:
             eps = self._eps_ptr(s)
-            mix = _lib.STRUCTS["FridoGuidanceCompose"](eps=eps, out=eps, weights=self.guide_w.data_ptr(), n=self.ncond, B=self.B,
-                                                       per_sample=self.H * self.W * plan.nch, rescale=int(self.rescale))
-            return list(plan.step.ops) + [(GUIDANCE_COMPOSE, mix)]
+            mix = _lib.make_op("FRIDO_OP_GUIDANCE_COMPOSE", eps=eps, out=eps, weights=self.guide_w.data_ptr(), n=self.ncond, B=self.B,
+                               per_sample=self.H * self.W * plan.nch, rescale=int(self.rescale))
+            return list(plan.step.ops) + [mix]
         if self.geo is None:
             return list(plan.step.ops)
-        from .patching import FOLD, UNFOLD
         fold = self.geo.fold_desc(plan.eps.data_ptr(), self.eps_full[s].data_ptr(), self.xrep * self.B, plan.nch)
-        return [(UNFOLD, self.unfold_x)] + list(plan.step.ops) + [(FOLD, fold)]
+        return [_lib.op_of("FRIDO_OP_UNFOLD", self.unfold_x)] + list(plan.step.ops) + [_lib.op_of("FRIDO_OP_FOLD", fold)]
 
     def _eps_ptr(self, s):
         return (self.eps_full[s] if self.geo is not None else self.stages[s].eps).data_ptr()
 
     def _update_op(self, s, noise=None, hist_mode=0, no_cfg=False):
-        """(op tag, descriptor) of stage s's state update on the engine's buffers, for its kind: the DDIM / PLMS step (hist_mode: how PLMS uses
-        its eps ring), the ancestral step, or (DPM_STEP, FridoDpmStep) with the stage's x0 history.  noise: None -- Philox in the kernel, keyed
-        by the device {seed, sample0} -- or (address, channels) of host noise [step][B][HW][channels] read by step index.  no_cfg: the eps is
-        already guidance-mixed (a score corrector ran); a composed engine's always is."""
+        """(kind name, fields) of stage s's state update on the engine's buffers, for its kind: the DDIM / PLMS step (hist_mode: how PLMS uses
+        its eps ring), the ancestral step, the DPM-Solver++ step with the stage's x0 history, or the inversion step.  noise: None -- Philox in
+        the kernel, keyed by the device {seed, sample0} -- or (address, channels) of host noise [step][B][HW][channels] read by step index.
+        no_cfg: the eps is already guidance-mixed (a score corrector ran); a composed engine's always is."""
         B, HW, C = self.B, self.H * self.W, self.C
         start, nch, eps = sum(self.embed[:s]), self.embed[s], self._eps_ptr(s)
         cfg2 = not self.composed and self.xrep == 2      # the update kernel mixes [cond | uncond] itself
-        if self.kind == "invert":       # (INVERT_STEP, FridoInvertStep): the stage's window only, no noise, no x0
-            return INVERT_STEP, _lib.STRUCTS["FridoInvertStep"](
+        if self.kind == "invert":       # the stage's window only, no noise, no x0
+            return "FRIDO_OP_INVERT_STEP", dict(
                 x=self.x.data_ptr(), eps_cond=eps, eps_uncond=eps + 4 * B * HW * nch if cfg2 else None, cfg_scale=self.cfg_scale,
                 cfg_dev=self.cfg_dev.data_ptr(), coef=self.coef.data_ptr(), step=self.step.data_ptr(), B=B, HW=HW, Cx=C, c_lo=start,
                 c_hi=start + nch)
@@ -452,7 +438,7 @@ class SamplerEngine:
             if cfg2 and not no_cfg:
                 kw["eps_uncond"] = eps + 4 * B * HW * nch
         if self.kind == "dpm":
-            return DPM_STEP, _lib.STRUCTS["FridoDpmStep"](x0_hist=self.x0_hist[s].data_ptr(), **kw)
+            return "FRIDO_OP_DPM_STEP", dict(kw, x0_hist=self.x0_hist[s].data_ptr())
         kw.update(write_x=1, temperature=self.temperature, rng_stream=s + 1, rng_dev=self.rng.data_ptr())
         if noise is not None:
             kw.update(noise=noise[0], noise_stride=B * HW * noise[1], noise_C=noise[1], noise_c0=start)
@@ -772,9 +758,9 @@ class SamplerEngine:
                 dst.copy_(m.to(self.dev, torch.float32).reshape(B, H * W))
 
     def _blend_op(self, s, window, masked, noise=None, clean=False):
-        """(KEEP_BLEND, FridoKeepBlend) on the engine's state: x <- q * m + (1 - m) * x on the channel window, q = q_sample(z0) at the device
-        step counter's row (clean: q = z0).  masked: stage s's mask, else m = 1.  noise: None -- Philox keyed by the device {seed, sample0},
-        draw = row + 1, stream EDIT_RNG_STREAM + s -- or (address, channels) of a host tape read by step index."""
+        """(kind name, fields) of the editing blend on the engine's state: x <- q * m + (1 - m) * x on the channel window, q = q_sample(z0) at
+        the device step counter's row (clean: q = z0).  masked: stage s's mask, else m = 1.  noise: None -- Philox keyed by the device
+        {seed, sample0}, draw = row + 1, stream EDIT_RNG_STREAM + s -- or (address, channels) of a host tape read by step index."""
         kw = dict(x=self.x.data_ptr(), z0=self.z0.data_ptr(), mask=self.masks[s].data_ptr() if masked else None, B=self.B, HW=self.H * self.W,
                   Cx=self.C, c0=window[0], c1=window[1], clean=int(clean))
         if not clean:
@@ -783,7 +769,7 @@ class SamplerEngine:
                 kw.update(noise=noise[0], noise_stride=self.B * self.H * self.W * noise[1], noise_C=noise[1])
             else:
                 kw.update(rng_dev=self.rng.data_ptr(), rng_stream=EDIT_RNG_STREAM + s)
-        return KEEP_BLEND, _lib.STRUCTS["FridoKeepBlend"](**kw)
+        return "FRIDO_OP_KEEP_BLEND", kw
 
     def _edit_stage(self, s, sp, o):
         """One stage of an edit: the last o.n rows of DDIM's chain (the device counter starts at row0 = n_steps - o.n) with the blends of
@@ -1084,11 +1070,9 @@ class DecoderRuntime(_Runtime):
 
     @_lib.with_planes
     def reconstruct(self, x, aux=False, use_graph=True):
-        """MSFPNVQModel.forward (msvqgan.py:166-186): encode program -> loss launcher -> decode program as ONE captured graph per
+        """MSFPNVQModel.forward (msvqgan.py:166-186): encode program -> codebook loss -> decode program as ONE captured graph per
         (B, H, W, aux), replayed on later batches; quant stays on the device between the halves.  aux: the three decodes of :168-177 as one
         decoder program at batch 3B.  Returns (dec (B or 3B, 3, H, W), quant, emb_loss, [idx_s])."""
-        from .patching import PatchProg
-        from .vqloss import VQLOSS
         B, Cin, H, W = x.shape
         x_in, enc, loss = self._encq(B, Cin, H, W)
         h, w = enc.quant.shape[2:]
@@ -1097,8 +1081,8 @@ class DecoderRuntime(_Runtime):
             x_in.copy_(x)
             key = ("rec", B, H, W, bool(aux), bool(use_graph))
             if key not in self.graphs:
-                prog = PatchProg(self.device, self.nsplit)
-                prog.ops = list(enc.prog.ops) + [(VQLOSS, loss.desc)] + list(dec.prog.ops)
+                prog = Prog(self.device, self.nsplit)
+                prog.ops = list(enc.prog.ops) + [_lib.op_of("FRIDO_OP_VQ_COMMIT_LOSS", loss.desc)] + list(dec.prog.ops)
                 prog.keep = [enc, loss, dec]
                 self.graphs[key] = prog.capture(sp) if use_graph else prog
                 self.graph_captures += 1

@@ -1,15 +1,11 @@
 """The MS-VQGAN's codebook loss on the HIP engine: frido_vq_commit_loss (frido_amd/csrc/vqloss.hip), the `emb_loss` of
-MSFPNVQModel.encode (taming/models/msvqgan.py:116-154; taming/modules/vqvae/quantize.py:286-291).  A launcher with a descriptor of its
-own, like the patch kernels and the diffusion objective's: inside a captured body it is an entry of a patching.PatchProg."""
+MSFPNVQModel.encode (taming/models/msvqgan.py:116-154; taming/modules/vqvae/quantize.py:286-291).  Op kind
+FRIDO_OP_VQ_COMMIT_LOSS inside a program; launch_vq_commit_loss is the one-launch form."""
 import ctypes as C
 
 import torch
 
 from . import _lib
-from .patching import FOREIGN
-
-VQLOSS = "vq_commit_loss"
-FOREIGN[VQLOSS] = "frido_vq_commit_loss"
 
 
 def launch_vq_commit_loss(desc, stream):

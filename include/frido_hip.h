@@ -41,8 +41,10 @@ typedef uint16_t frido_bf16;
  * struct's END (a split-K GEMM's reduction finished by the GroupNorm launch that consumes its output).  5 (r05): FridoAttnSmall.skip_act_store
  * at the struct's END; frido_status_flags(&word, clear) (sticky saturation / non-finite flags; clear = 1 resets them).
  * 7: the multi-head flash attention descriptor FridoAttnMh, its launcher frido_attn_mh and the op kind FRIDO_OP_ATTN_MH were ADDED (no existing struct moved).
- * 7, no layout change: FridoSamplerStep.hist_mode gained the VALUE FRIDO_STEP_ANCESTRAL (the DDPM ancestral update; every other mode computes the same bits). */
-#define FRIDO_ABI_VERSION 7
+ * 7, no layout change: FridoSamplerStep.hist_mode gained the VALUE FRIDO_STEP_ANCESTRAL (the DDPM ancestral update; every other mode computes the same bits).
+ * 8: nine launchers that had descriptors but no op kind became op kinds, APPENDED as 27 .. 35 (FRIDO_OP_UNFOLD .. FRIDO_OP_GUIDANCE_COMPOSE; no
+ * existing kind or struct moved, sizeof(FridoOp) unchanged); the FRIDO_DESC_* codes of frido_sizeof_desc are gone, it takes the op kind. */
+#define FRIDO_ABI_VERSION 8
 #define FRIDO_SPLITK_HEADER_BYTES 65536     /* the ticket header at the start of a split-K workspace; partial sums follow: [splitk][M][N] f32 */
 
 #define FRIDO_OK 0
@@ -429,8 +431,7 @@ typedef struct FridoFill { uint32_t* dst; int64_t n; uint32_t value; } FridoFill
 typedef struct FridoSync { int32_t from, to; } FridoSync;
 
 /* ---- patch-wise ("convolutional") mode: FridoDiffusion.split_input_params (frido/models/diffusion/frido.py:714-764, 1076-1152) ----
- * Not op kinds: exported launchers with descriptors of their own (frido_unfold / frido_fold below); a step body that contains them
- * is captured between frido_capture_begin and frido_capture_end.
+ * FRIDO_OP_UNFOLD / FRIDO_OP_FOLD (launchers frido_unfold / frido_fold below): a step body that contains them is a program like any other.
  *
  * Crops of an NHWC f32 map src[B][H][W][C]: dst[Bc][kh][kw][C], Bc = B * L, L = Ly * Lx, Ly = (H - kh) / sy + 1, Lx = (W - kw) / sx + 1
  * (both divisions exact).  Crop l = ly * Lx + lx starts at (ly * sy, lx * sx) -- nn.Unfold's order.
@@ -449,8 +450,7 @@ typedef struct FridoFold { const float* crops; float* out; const float* wt; cons
                            int32_t B, H, W, C, kh, kw, sy, sx, u8_mode; } FridoFold;
 
 /* ---- the diffusion objective: FridoDiffusion.forward / p_losses (frido/models/diffusion/frido.py:1007-1050, 1180-1224) ----
- * Not op kinds either: two exported launchers with descriptors of their own (frido_qsample / frido_diffusion_loss below), run eagerly or
- * between frido_capture_begin and frido_capture_end.  Both take their noise as a tape [B][HW][Cx] (NHWC f32, the full latent) or, with
+ * FRIDO_OP_QSAMPLE / FRIDO_OP_DIFFUSION_LOSS (launchers frido_qsample / frido_diffusion_loss below).  Both take their noise as a tape [B][HW][Cx] (NHWC f32, the full latent) or, with
  * noise == NULL, draw it: Philox4x32-10 in frido_randn's numbering -- 4-float groups over the flat sample [HW][Cx] (HW * Cx a multiple
  * of 4), key (seed, sample0 + b, rng_stream); rng_dev, an optional device {seed, sample0}, overrides the two fields (graph replay).
  * t is a device int64 [B]; a value outside [0, T) reads the nearest table row.
@@ -483,8 +483,7 @@ typedef struct FridoDiffusionLoss { const float* pred; const int64_t* t; const f
 
 /* ---- the MS-VQGAN's codebook loss: MSFPNVQModel.encode (taming/models/msvqgan.py:116-154), VectorQuantizer2.forward
  * (taming/modules/vqvae/quantize.py:286-291) ----
- * Not an op kind: an exported launcher with a descriptor of its own (frido_vq_commit_loss below), run eagerly or between
- * frido_capture_begin and frido_capture_end.  Up to FRIDO_VQLOSS_MAX_SCALES scales, coarse first; scale k compares the channel slice
+ * FRIDO_OP_VQ_COMMIT_LOSS (launcher frido_vq_commit_loss below).  Up to FRIDO_VQLOSS_MAX_SCALES scales, coarse first; scale k compares the channel slice
  * [c0, c0 + e) of two NHWC f32 maps z[k], zq[k] of npix[k] rows C[k] wide (z: the quantiser's input, zq: its output):
  *   m_k = mean over npix * e elements of (zq - z)^2 -- difference and square in fp32, each rounded on its own, the sum in f64 in a fixed
  *         order (no atomics: the same bits on every launch; the order depends on the scale's own size only, so m_k does not depend on
@@ -501,8 +500,7 @@ typedef struct FridoVqCommitLoss { const float* z[4]; const float* zq[4]; int64_
                                    double* partials; float* out; float* emb_loss; float beta; int32_t n_scales, legacy; } FridoVqCommitLoss;
 
 /* ---- DPM-Solver++(2M): the second-order multistep solver in data prediction (Lu et al. 2022), not in the reference ----
- * Not an op kind: an exported launcher with a descriptor of its own (frido_dpm_step below), run eagerly or between frido_capture_begin and
- * frido_capture_end.  One update of the NHWC f32 state x[B][HW][Cx] on the active stage channels [start, start + nch); what
+ * FRIDO_OP_DPM_STEP (launcher frido_dpm_step below).  One update of the NHWC f32 state x[B][HW][Cx] on the active stage channels [start, start + nch); what
  * FridoSamplerStep carries for DDIM minus noise and PLMS history, plus x0_hist[B * HW][nch], the previous step's x0 prediction.
  * The 8-float row coef[*step + coef_row_offset] = {inv_alpha, sigma, c_x, c_d, w_cur, w_last, pad, pad} (frido_amd/schedules.py
  * dpm_solver_table; step NULL reads as 0).  Per active element in fp32, every product and sum rounded on its own (no contraction):
@@ -525,8 +523,7 @@ typedef struct FridoDpmStep {
 
 /* ---- DDIM editing: the img2img start and the keep-mask blend of an inpainting loop (frido/models/diffusion/ddim.py:158-161 with
  * q_sample, frido/models/diffusion/frido.py:302-318) ----
- * Not an op kind: an exported launcher with a descriptor of its own (frido_keep_blend below), run eagerly or between frido_capture_begin and
- * frido_capture_end.  One pass over the NHWC f32 state x[B][HW][Cx], in place, on the channel window [c0, c1); in fp32, every product and
+ * FRIDO_OP_KEEP_BLEND (launcher frido_keep_blend below).  One pass over the NHWC f32 state x[B][HW][Cx], in place, on the channel window [c0, c1); in fp32, every product and
  * sum rounded on its own (no contraction):
  *   q  = sa * z0[b][p][c] + sb * n
  *   x' = q * m[b][p] + (1 - m[b][p]) * x
@@ -551,13 +548,10 @@ typedef struct FridoKeepBlend {
     const int64_t* rng_dev; uint64_t seed; int64_t sample0;
     int32_t B, HW, Cx, c0, c1, row_offset, noise_C, rng_stream, clean;
 } FridoKeepBlend;
-/* frido_sizeof_desc() code of a descriptor that belongs to no op kind */
-#define FRIDO_DESC_KEEP_BLEND 1001
 
 /* ---- DDIM inversion: the deterministic encoder of DDIM (the probability-flow ODE walked upwards; upstream latent-diffusion's
  * DDIMSampler.encode), not in the reference ----
- * Not an op kind: an exported launcher with a descriptor of its own (frido_invert_step below), run eagerly or between frido_capture_begin
- * and frido_capture_end.  One pass over the NHWC f32 state x[B][HW][Cx], in place, on the channel window [c_lo, c_hi) -- the stage's own
+ * FRIDO_OP_INVERT_STEP (launcher frido_invert_step below).  One pass over the NHWC f32 state x[B][HW][Cx], in place, on the channel window [c_lo, c_hi) -- the stage's own
  * channels; eps_cond / eps_uncond are the denoiser's output [B * HW][c_hi - c_lo].  {c0, c1} = coef[*step + coef_row_offset] of the 2-float
  * rows of frido_amd/schedules.py ddim_inversion_table (step NULL reads as 0).  Per element in fp32, every product and sum rounded on its
  * own (no contraction):
@@ -571,13 +565,11 @@ typedef struct FridoInvertStep {
     const float* coef; const int32_t* step;
     int32_t B, HW, Cx, c_lo, c_hi, coef_row_offset; float cfg_scale;
 } FridoInvertStep;
-#define FRIDO_DESC_INVERT_STEP 1002
 
 /* ---- composed guidance: several weighted conditionings against one unconditional evaluation (Liu et al. 2022, "Compositional Visual
  * Generation with Composable Diffusion Models"; a negative weight negates) and the guidance rescale of Lin et al. 2024, not in the
  * reference ----
- * Not an op kind: an exported launcher with a descriptor of its own (frido_guidance_compose below), run eagerly or between
- * frido_capture_begin and frido_capture_end.  eps holds n + 1 slots of B * per_sample floats: slot i < n the denoiser's output under
+ * FRIDO_OP_GUIDANCE_COMPOSE (launcher frido_guidance_compose below).  eps holds n + 1 slots of B * per_sample floats: slot i < n the denoiser's output under
  * conditioning i, slot n the unconditional one (the [cond | uncond] batch layout of the sampling engine for n = 1).  weights points to
  * n + 1 DEVICE floats, w_0 .. w_{n-1} then phi, read by the kernel (other weights replay the same graph).  Per element in fp32, every
  * product and sum rounded on its own (no contraction):
@@ -595,12 +587,13 @@ typedef struct FridoGuidanceCompose {
     const float* weights;        /* device: w_0 .. w_{n-1}, phi */
     int32_t n, B, per_sample, rescale;
 } FridoGuidanceCompose;
-#define FRIDO_DESC_GUIDANCE_COMPOSE 1003
 
 enum FridoOpKind {
     FRIDO_OP_GEMM = 1, FRIDO_OP_GN_STATS, FRIDO_OP_GN_APPLY, FRIDO_OP_LAYERNORM, FRIDO_OP_SOFTMAX,
     FRIDO_OP_GEGLU, FRIDO_OP_PACK, FRIDO_OP_RELAYOUT, FRIDO_OP_VQ, FRIDO_OP_SAMPLER_STEP,
-    FRIDO_OP_HANDOFF, FRIDO_OP_RANDN, FRIDO_OP_STEP_ADD, FRIDO_OP_FILL, FRIDO_OP_TIME_EMB, FRIDO_OP_CONVT, FRIDO_OP_PLACE, FRIDO_OP_EMBED, FRIDO_OP_TO_U8, FRIDO_OP_ATTN_SMALL, FRIDO_OP_GN_FUSED, FRIDO_OP_COPY, FRIDO_OP_ATTN_FLASH, FRIDO_OP_SYNC, FRIDO_OP_L2NORM, FRIDO_OP_ATTN_MH, FRIDO_OP__COUNT
+    FRIDO_OP_HANDOFF, FRIDO_OP_RANDN, FRIDO_OP_STEP_ADD, FRIDO_OP_FILL, FRIDO_OP_TIME_EMB, FRIDO_OP_CONVT, FRIDO_OP_PLACE, FRIDO_OP_EMBED, FRIDO_OP_TO_U8, FRIDO_OP_ATTN_SMALL, FRIDO_OP_GN_FUSED, FRIDO_OP_COPY, FRIDO_OP_ATTN_FLASH, FRIDO_OP_SYNC, FRIDO_OP_L2NORM, FRIDO_OP_ATTN_MH,
+    FRIDO_OP_UNFOLD, FRIDO_OP_FOLD, FRIDO_OP_QSAMPLE, FRIDO_OP_DIFFUSION_LOSS, FRIDO_OP_VQ_COMMIT_LOSS, FRIDO_OP_DPM_STEP, FRIDO_OP_KEEP_BLEND,
+    FRIDO_OP_INVERT_STEP, FRIDO_OP_GUIDANCE_COMPOSE, FRIDO_OP__COUNT
 };
 
 /* A program is an array of tagged ops executed in order on one stream by the native executor. */
@@ -611,6 +604,8 @@ typedef struct FridoOp {
         FridoSoftmax softmax; FridoGeglu geglu; FridoPack pack; FridoRelayout relayout; FridoVq vq;
         FridoSamplerStep sampler_step; FridoHandoff handoff; FridoRandn randn; FridoStepAdd step_add;
         FridoFill fill; FridoTimeEmb time_emb; FridoConvT convt; FridoPlace place; FridoEmbed embed; FridoToU8 to_u8; FridoAttnSmall attn_small; FridoCopy copy; FridoSync sync; FridoL2Norm l2norm; FridoAttnMh attn_mh;
+        FridoUnfold unfold; FridoFold fold; FridoQSample qsample; FridoDiffusionLoss diffusion_loss; FridoVqCommitLoss vq_commit_loss;
+        FridoDpmStep dpm_step; FridoKeepBlend keep_blend; FridoInvertStep invert_step; FridoGuidanceCompose guidance_compose;
         char _size[512];
     } u;
 } FridoOp;
@@ -673,7 +668,7 @@ int frido_graph_capture(const FridoOp* ops, int32_t n, frido_stream_t s, void** 
 int frido_graph_launch(void* graph, frido_stream_t s);
 int frido_graph_destroy(void* graph);
 /* The two halves of frido_graph_capture (= begin + frido_run + end): whatever the caller launches on `s` in between -- frido_run
- * programs, frido_unfold / frido_fold -- becomes ONE graph, instantiated by frido_capture_end (*graph: the handle frido_graph_launch /
+ * programs, single-op launchers -- becomes ONE graph, instantiated by frido_capture_end (*graph: the handle frido_graph_launch /
  * frido_graph_destroy take).  frido_capture_end must be called after a successful begin even when a launch in between failed (it ends
  * the capture); it then returns an error and no graph. */
 int frido_capture_begin(frido_stream_t s);
@@ -718,8 +713,7 @@ int frido_abi_version(void);
  * A host that packs weights / operands itself (hi = round(v), lo = round(v - hi) in this format) asks here. */
 int frido_x3_plane_format(void);
 int frido_sizeof_op(void);             /* sizeof(FridoOp): checked by the ctypes mirror */
-int frido_sizeof_desc(int32_t kind);   /* sizeof of the descriptor struct of that op kind (or of FRIDO_DESC_KEEP_BLEND / FRIDO_DESC_INVERT_STEP /
-                                          FRIDO_DESC_GUIDANCE_COMPOSE) */
+int frido_sizeof_desc(int32_t kind);   /* sizeof of the descriptor struct of that op kind, -1 for an unknown kind */
 const char* frido_last_error(void);
 /* Sticky numerics status of the CURRENT device (r05): kernels cannot return errors, so operand producers and normalisation kernels
  * OR bits into a device word when they meet a value the arithmetic cannot represent, and this call reads it back (it synchronises

@@ -1,5 +1,5 @@
 """CPU-side checks of ancestral (DDPM) sampling: the posterior schedule tables against the reference's own buffers (anc_tables.npz), the
-loop-order coefficient rows of the update kernel, the public methods' signatures, the unchanged ABI 7 layout with the new hist_mode
+loop-order coefficient rows of the update kernel, the public methods' signatures, the unchanged descriptor layout (ABI 8 now) with the new hist_mode
 value, the launcher's argument checks (no device is touched), and the options that are refused by name."""
 import ctypes as C
 import inspect
@@ -87,14 +87,15 @@ def test_posterior_helpers_match_the_reference_on_any_device():
     assert torch.equal(qv, torch.from_numpy(g["qp_var"])) and torch.equal(ql, torch.from_numpy(g["qp_logvar"]))
 
 
-def test_abi_stays_7_and_the_step_descriptor_keeps_its_layout():
-    assert _lib.ABI_VERSION == 7
-    assert C.sizeof(_lib.STRUCTS["FridoSamplerStep"]) == 232 and C.sizeof(_lib.FridoOp) == 520      # the parent's sizes
-    assert _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == _lib.OP_KINDS["FRIDO_OP__COUNT"] - 1                # no op kind was added
+def test_abi_is_8_and_the_step_descriptor_keeps_its_layout():
+    assert _lib.ABI_VERSION == 8
+    assert C.sizeof(_lib.STRUCTS["FridoSamplerStep"]) == 232 and C.sizeof(_lib.FridoOp) == 520      # the sizes of ABI 7
+    assert _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == 26 and _lib.OP_KINDS["FRIDO_OP__COUNT"] == 36       # the ancestral update added no kind: ABI 8's nine follow ATTN_MH
+    assert _lib.OP_KINDS["FRIDO_OP_SAMPLER_STEP"] == 10
     assert _lib.STEP_ANCESTRAL not in (0, 1, 3) and _lib.STEP_ANCESTRAL & 3 == 0                    # cannot be read as a ring mode
     for planes in ("f16", "bf16"):
         L = _lib.lib(planes)
-        assert L.frido_abi_version() == 7
+        assert L.frido_abi_version() == 8
         assert L.frido_sizeof_desc(_lib.OP_KINDS["FRIDO_OP_SAMPLER_STEP"]) == 232
 
 

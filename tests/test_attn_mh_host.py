@@ -1,4 +1,4 @@
-"""CPU-side checks of the multi-head attention op (ABI 7): the header, its ctypes mirror and both builds of the library agree on the
+"""CPU-side checks of the multi-head attention op (added in ABI 7): the header, its ctypes mirror and both builds of the library agree on the
 descriptor, the launcher rejects what it cannot run without touching a device, and the builder refuses unsupported head dimensions."""
 import ctypes as C
 
@@ -14,9 +14,10 @@ def _desc(**over):
     return _lib.make_op("FRIDO_OP_ATTN_MH", **kw)[1]
 
 
-def test_abi_7_declares_the_multi_head_attention_op():
-    assert _lib.ABI_VERSION == 7
-    assert _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == _lib.OP_KINDS["FRIDO_OP__COUNT"] - 1 == _lib.OP_KINDS["FRIDO_OP_L2NORM"] + 1      # appended
+def test_abi_declares_the_multi_head_attention_op():
+    assert _lib.ABI_VERSION == 8
+    assert _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == 26 == _lib.OP_KINDS["FRIDO_OP_L2NORM"] + 1      # appended in ABI 7
+    assert _lib.OP_KINDS["FRIDO_OP__COUNT"] == 36 and _lib.OP_KINDS["FRIDO_OP_UNFOLD"] == 27    # ABI 8's nine kinds follow it
     assert _lib.KIND_STRUCT["FRIDO_OP_ATTN_MH"] == "FridoAttnMh"
     fields = [f for f, _ in _lib.STRUCTS["FridoAttnMh"]._fields_]
     assert {"heads", "q_hs", "k_hs", "ldvt", "alpha"} <= set(fields)
@@ -24,7 +25,7 @@ def test_abi_7_declares_the_multi_head_attention_op():
     assert {"frido_attn_mh", "frido_attn_mh_supported"} <= set(_lib.declared_symbols()) and "frido_attn_mh" in _lib.EXPORTS
     for planes in ("f16", "bf16"):
         L = _lib.lib(planes)
-        assert L.frido_abi_version() == 7
+        assert L.frido_abi_version() == 8
         assert L.frido_sizeof_desc(_lib.OP_KINDS["FRIDO_OP_ATTN_MH"]) == C.sizeof(_lib.STRUCTS["FridoAttnMh"])
         assert [x for x in range(8, 264, 8) if L.frido_attn_mh_supported(x)] == [32, 64]
 

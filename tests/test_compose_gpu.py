@@ -445,7 +445,9 @@ def test_replay_other_weights_and_a_plain_call_in_between(ctx_model):
     eng, = _engines(model)
     assert list(_cache(model))[-1] == ("ddim", B, 6, 16, 16, 5, S, 0.0, True, 2, 1.0, 0, ("compose", 3, True))
     captures = eng.graph_captures
-    assert captures == 2 and all(any(op[0] == "guidance_compose" for op in g.keep[1].ops) for g in eng.graphs.values())
+    from frido_amd import _lib
+    mix = _lib.OP_KINDS["FRIDO_OP_GUIDANCE_COMPOSE"]
+    assert captures == 2 and all(any(op[0] == mix for op in g.keep[1].ops) for g in eng.graphs.values())
     second, _ = _sample(model, "ddim", c, uc, **kw)
     assert torch.equal(_bits(second), _bits(first)) and eng.graph_captures == captures
     kw2 = dict(compose=[(c1, 0.25), (c2, -1.25)], guidance_rescale=0.3)
@@ -454,7 +456,7 @@ def test_replay_other_weights_and_a_plain_call_in_between(ctx_model):
     plain_after, _ = _sample(model, "ddim", c, uc)
     assert torch.equal(_bits(plain_after), _bits(plain_before)) and len(_cache(model)) == 2
     plain_eng, = _engines(model, composed=False)
-    assert plain_eng.xrep == 2 and not any(op[0] == "guidance_compose" for g in plain_eng.graphs.values() for op in g.keep[1].ops)
+    assert plain_eng.xrep == 2 and not any(op[0] == mix for g in plain_eng.graphs.values() for op in g.keep[1].ops)
     _cache(model).clear()
     fresh, _ = _sample(model, "ddim", c, uc, scale=2.5, **kw2)
     assert torch.equal(_bits(fresh), _bits(other))

@@ -1,5 +1,5 @@
 """CPU-side checks of composed guidance (compose= / guidance_rescale=): the launcher in the header and in both builds, its argument checks
-(no device is touched), the unchanged ABI 7 layout, every ValueError and by-name refusal of the public keywords, the engine-cache key of a
+(no device is touched), its op kind in ABI 8, every ValueError and by-name refusal of the public keywords, the engine-cache key of a
 call without them, and the arithmetic on an analytic equal-variance Gaussian family in float64."""
 import ctypes as C
 
@@ -14,25 +14,27 @@ LINEAR = dict(linear_start=0.0015, linear_end=0.0155)      # the shipped schedul
 
 
 # ---- 1. the launcher and the ABI ------------------------------------------------------------------------------------------------------
-def test_header_declares_the_launcher_and_abi_7_is_untouched():
+def test_header_declares_the_launcher_and_its_op_kind():
     assert "frido_guidance_compose" in _lib.declared_symbols() and "frido_guidance_compose" in _lib.EXPORTS
-    assert _lib.ABI_VERSION == 7
-    assert _lib.OP_KINDS["FRIDO_OP__COUNT"] == 27 and _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == 26
+    assert _lib.ABI_VERSION == 8
+    assert _lib.OP_KINDS["FRIDO_OP__COUNT"] == 36 and _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == 26
     assert C.sizeof(_lib.FridoOp) == 520 and C.sizeof(_lib.STRUCTS["FridoSamplerStep"]) == 232
     assert C.sizeof(_lib.STRUCTS["FridoDpmStep"]) == 112 and C.sizeof(_lib.STRUCTS["FridoKeepBlend"]) == 120
-    assert C.sizeof(_lib.STRUCTS["FridoInvertStep"]) == 80 and _lib.DESC_INVERT_STEP == 1002 and _lib.DESC_KEEP_BLEND == 1001
-    assert "FridoGuidanceCompose" in _lib.STRUCTS and "FridoGuidanceCompose" not in _lib.KIND_STRUCT.values()      # no op kind
-    assert C.sizeof(_lib.STRUCTS["FridoGuidanceCompose"]) == 40 and _lib.DESC_GUIDANCE_COMPOSE == 1003
-    assert patching.FOREIGN[runtime.GUIDANCE_COMPOSE] == "frido_guidance_compose"
+    assert C.sizeof(_lib.STRUCTS["FridoInvertStep"]) == 80
+    assert _lib.OP_KINDS["FRIDO_OP_GUIDANCE_COMPOSE"] == 35 and _lib.KIND_STRUCT["FRIDO_OP_GUIDANCE_COMPOSE"] == "FridoGuidanceCompose"
+    assert _lib.OP_KINDS["FRIDO_OP_INVERT_STEP"] == 34 and _lib.KIND_STRUCT["FRIDO_OP_INVERT_STEP"] == "FridoInvertStep"
+    assert _lib.OP_KINDS["FRIDO_OP_KEEP_BLEND"] == 33 and _lib.KIND_STRUCT["FRIDO_OP_KEEP_BLEND"] == "FridoKeepBlend"
+    assert C.sizeof(_lib.STRUCTS["FridoGuidanceCompose"]) == 40
     assert runtime.GUIDANCE_MAX == samplers.COMPOSE_MAX + 1 == 8
 
 
 @pytest.mark.parametrize("planes", ["f16", "bf16"])
 def test_both_builds_export_the_launcher_and_agree_on_the_struct_size(planes):
     L = _lib.lib(planes)
-    assert hasattr(L, "frido_guidance_compose") and hasattr(L, patching.FOREIGN[runtime.GUIDANCE_COMPOSE])
-    assert L.frido_sizeof_desc(1003) == C.sizeof(_lib.STRUCTS["FridoGuidanceCompose"])
-    assert L.frido_abi_version() == 7
+    assert hasattr(L, "frido_guidance_compose")
+    assert L.frido_sizeof_desc(_lib.OP_KINDS["FRIDO_OP_GUIDANCE_COMPOSE"]) == L.frido_sizeof_desc(35) == C.sizeof(_lib.STRUCTS["FridoGuidanceCompose"])
+    assert L.frido_sizeof_desc(1003) == -1      # the kind-less descriptor code of ABI 7 is gone
+    assert L.frido_abi_version() == 8
 
 
 EPS, TOTAL = 0x100000, 3 * 105 * 4        # slot 0's address; bytes per slot of G_OK

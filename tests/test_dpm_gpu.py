@@ -148,9 +148,8 @@ def test_nonfinite_state_raises_the_status_bit():
 def test_captured_graph_replayed_twice_equals_two_eager_launches(planes):
     """[frido_dpm_step, counter add] captured once and replayed twice: the device counter moves the replays from the first-order row 0 to
     the second-order row 1, which reads the history the first replay wrote."""
-    from frido_amd import _lib, runtime
-    from frido_amd.engine import require_gpu
-    from frido_amd.patching import PatchProg
+    from frido_amd import _lib
+    from frido_amd.engine import Prog, require_gpu
     Bk, HW, Cx, start, nch = GEOMETRIES["vec_s4n4"]
     tab = _table()
     f = lambda tag, c: torch.from_numpy(seeded_normal(f"dpmk:graph:{tag}", (Bk, HW, c))).cuda()
@@ -164,8 +163,8 @@ def test_captured_graph_replayed_twice_equals_two_eager_launches(planes):
             step = torch.zeros(1, dtype=torch.int32, device="cuda")
             d = _lib.STRUCTS["FridoDpmStep"](x=x.data_ptr(), B=Bk, HW=HW, Cx=Cx, start=start, nch=nch, eps_cond=e_c.data_ptr(), coef=coef.data_ptr(),
                                               step=step.data_ptr(), x_out=x.data_ptr(), x0_hist=hist.data_ptr())
-            p = PatchProg(dev, 2)
-            p.ops = [(runtime.DPM_STEP, d)]
+            p = Prog(dev, 2)
+            p.ops = [_lib.op_of("FRIDO_OP_DPM_STEP", d)]
             p.emit("FRIDO_OP_STEP_ADD", step=step.data_ptr(), delta=1)
             stream = torch.cuda.Stream()
             stream.wait_stream(torch.cuda.current_stream())

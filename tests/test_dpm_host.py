@@ -1,6 +1,6 @@
 """CPU-side checks of the DPM-Solver++(2M) sampler: the coefficient table's identities in float64, the solver's order of convergence on an
 analytic Gaussian data model (a float64 loop of the test's own over the table), the logSNR grid, every refusal with its name, the
-launcher in the header and in both builds, its argument checks (no device is touched) and the unchanged ABI 7 layout."""
+launcher in the header and in both builds, its argument checks (no device is touched) and its op kind in ABI 8."""
 import ctypes as C
 
 import numpy as np
@@ -207,16 +207,18 @@ def test_pipeline_refuses_an_eta_for_the_solver():
         sample_images(_model(), CTX, S=6, sampler="dpm", eta=0.5)
 
 
-def test_header_declares_the_launcher_and_abi_7_is_untouched():
+def test_header_declares_the_launcher_and_its_op_kind():
     assert "frido_dpm_step" in _lib.declared_symbols() and "frido_dpm_step" in _lib.EXPORTS
-    assert _lib.ABI_VERSION == 7
-    assert _lib.OP_KINDS["FRIDO_OP__COUNT"] == 27 and _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == 26
+    assert _lib.ABI_VERSION == 8
+    assert _lib.OP_KINDS["FRIDO_OP__COUNT"] == 36 and _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == 26
     assert C.sizeof(_lib.FridoOp) == 520 and C.sizeof(_lib.STRUCTS["FridoGemm"]) == 512
     assert C.sizeof(_lib.STRUCTS["FridoSamplerStep"]) == 232
-    assert "FridoDpmStep" not in _lib.KIND_STRUCT.values()      # a launcher of its own, not an op kind
+    assert _lib.OP_KINDS["FRIDO_OP_DPM_STEP"] == 32 and _lib.KIND_STRUCT["FRIDO_OP_DPM_STEP"] == "FridoDpmStep"
     assert C.sizeof(_lib.STRUCTS["FridoDpmStep"]) == 112
-    from frido_amd import patching, runtime
-    assert patching.FOREIGN[runtime.DPM_STEP] == "frido_dpm_step"
+    for planes in ("f16", "bf16"):
+        L = _lib.lib(planes)
+        assert L.frido_abi_version() == 8
+        assert L.frido_sizeof_desc(32) == C.sizeof(_lib.STRUCTS["FridoDpmStep"]) and hasattr(L, "frido_dpm_step")
 
 
 def test_both_builds_export_the_launcher():

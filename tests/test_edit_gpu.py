@@ -195,9 +195,8 @@ def test_philox_draws_are_standard_normal():
 def test_captured_body_with_the_device_counter_and_rng_equals_eager(planes):
     """[blend, counter add] captured once and replayed three times from row 1: the device counter moves every replay to its own
     coefficient row and Philox draw, rng_dev carries the key; the replay equals the eager run bit for bit, and rows differ."""
-    from frido_amd import _lib, runtime
-    from frido_amd.engine import require_gpu
-    from frido_amd.patching import PatchProg
+    from frido_amd import _lib
+    from frido_amd.engine import Prog, require_gpu
     Bk, HW, Cx, c0, c1 = GEOMETRIES["b3_5x7_c6_w36"]
     f = lambda tag, *shape: torch.from_numpy(seeded_normal(f"editk:graph:{tag}", shape)).cuda()
     x_init, z0, m = f("x", Bk, HW, Cx), f("z0", Bk, HW, Cx), f("m", Bk, HW).sigmoid()
@@ -210,8 +209,8 @@ def test_captured_body_with_the_device_counter_and_rng_equals_eager(planes):
             x, step = x_init.clone(), torch.full((1,), 1, dtype=torch.int32, device="cuda")
             d = _lib.STRUCTS["FridoKeepBlend"](x=x.data_ptr(), z0=z0.data_ptr(), mask=m.data_ptr(), qtab=qtab.data_ptr(), step=step.data_ptr(),
                                                 rng_dev=rng.data_ptr(), rng_stream=65, B=Bk, HW=HW, Cx=Cx, c0=c0, c1=c1)
-            p = PatchProg(dev, 2)
-            p.ops = [(runtime.KEEP_BLEND, d)]
+            p = Prog(dev, 2)
+            p.ops = [_lib.op_of("FRIDO_OP_KEEP_BLEND", d)]
             p.emit("FRIDO_OP_STEP_ADD", step=step.data_ptr(), delta=1)
             stream = torch.cuda.Stream()
             stream.wait_stream(torch.cuda.current_stream())

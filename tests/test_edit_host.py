@@ -1,5 +1,5 @@
 """CPU-side checks of DDIM editing (img2img start, keep-mask inpainting): the launcher in the header and in both builds, its argument
-checks (no device is touched), the unchanged ABI 7 layout, every refusal of `edit` with its name, the k-from-strength rule, the per-stage
+checks (no device is touched), its op kind in ABI 8, every refusal of `edit` with its name, the k-from-strength rule, the per-stage
 min-pooled masks, the replay units of a chain that starts past row 0, and the order of the host-noise draws of a stage."""
 import ctypes as C
 
@@ -11,16 +11,15 @@ from frido_amd import _lib, patching, runtime, samplers
 
 
 # ---- the launcher and the ABI ---------------------------------------------------------------------------------------------------------
-def test_header_declares_the_launcher_and_abi_7_is_untouched():
+def test_header_declares_the_launcher_and_its_op_kind():
     assert "frido_keep_blend" in _lib.declared_symbols() and "frido_keep_blend" in _lib.EXPORTS
-    assert _lib.ABI_VERSION == 7
-    assert _lib.OP_KINDS["FRIDO_OP__COUNT"] == 27 and _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == 26
+    assert _lib.ABI_VERSION == 8
+    assert _lib.OP_KINDS["FRIDO_OP__COUNT"] == 36 and _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == 26
     assert C.sizeof(_lib.FridoOp) == 520 and C.sizeof(_lib.STRUCTS["FridoGemm"]) == 512
     assert C.sizeof(_lib.STRUCTS["FridoSamplerStep"]) == 232 and C.sizeof(_lib.STRUCTS["FridoDpmStep"]) == 112
     assert C.sizeof(_lib.STRUCTS["FridoQSample"]) == 112
-    assert "FridoKeepBlend" not in _lib.KIND_STRUCT.values()      # a launcher of its own, not an op kind
+    assert _lib.OP_KINDS["FRIDO_OP_KEEP_BLEND"] == 33 and _lib.KIND_STRUCT["FRIDO_OP_KEEP_BLEND"] == "FridoKeepBlend"
     assert C.sizeof(_lib.STRUCTS["FridoKeepBlend"]) == 120
-    assert patching.FOREIGN[runtime.KEEP_BLEND] == "frido_keep_blend"
     assert runtime.EDIT_RNG_STREAM == 64
 
 
@@ -28,8 +27,9 @@ def test_header_declares_the_launcher_and_abi_7_is_untouched():
 def test_both_builds_export_the_launcher_and_agree_on_the_struct_size(planes):
     L = _lib.lib(planes)
     assert hasattr(L, "frido_keep_blend")
-    assert L.frido_sizeof_desc(_lib.DESC_KEEP_BLEND) == C.sizeof(_lib.STRUCTS["FridoKeepBlend"])
-    assert L.frido_abi_version() == 7
+    assert L.frido_sizeof_desc(_lib.OP_KINDS["FRIDO_OP_KEEP_BLEND"]) == L.frido_sizeof_desc(33) == C.sizeof(_lib.STRUCTS["FridoKeepBlend"])
+    assert L.frido_sizeof_desc(1001) == -1      # the kind-less descriptor code of ABI 7 is gone
+    assert L.frido_abi_version() == 8
 
 
 K_OK = dict(x=0x1000, z0=0x2000, mask=0x3000, qtab=0x4000, step=0x5000, B=3, HW=35, Cx=6, c0=3, c1=6, row_offset=2, rng_stream=65)

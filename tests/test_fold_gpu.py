@@ -116,9 +116,10 @@ def test_u8_output_is_both_formulas_applied_to_the_f32_fold(Cn, mode, conv):
     assert 0 in want and 255 in want and torch.equal(u8.cpu(), want) and torch.equal(only.cpu(), want)
 
 
-def test_fold_replayed_from_a_bracketed_graph_equals_the_direct_launch():
-    """frido_capture_begin / frido_capture_end around unfold -> a frido_run program -> fold: one graph, replayed on new data."""
-    from frido_amd.engine import require_gpu
+def test_fold_replayed_from_a_captured_program_equals_the_direct_launch():
+    """[FRIDO_OP_UNFOLD, FRIDO_OP_COPY, FRIDO_OP_FOLD] as one program: run, then captured as one graph and replayed on new data."""
+    from frido_amd import _lib
+    from frido_amd.engine import Prog, require_gpu
     dev = require_gpu("cuda")
     geo = _geo(16, 16, 8, 8, 4, 4, False)
     B, Cn = 2, 6
@@ -127,10 +128,10 @@ def test_fold_replayed_from_a_bracketed_graph_equals_the_direct_launch():
     crops = torch.zeros(B * geo.L, 8, 8, Cn, device="cuda")
     moved = torch.zeros_like(crops)
     out = torch.zeros(B, 16, 16, Cn, device="cuda")
-    prog = patching.PatchProg(dev, 2)
-    prog.ops.append((patching.UNFOLD, geo.unfold_desc(xs.data_ptr(), crops.data_ptr(), B, Cn)))
+    prog = Prog(dev, 2)
+    prog.ops.append(_lib.op_of("FRIDO_OP_UNFOLD", geo.unfold_desc(xs.data_ptr(), crops.data_ptr(), B, Cn)))
     prog.emit("FRIDO_OP_COPY", src=crops.data_ptr(), dst=moved.data_ptr(), n=crops.numel() * 4)
-    prog.ops.append((patching.FOLD, geo.fold_desc(moved.data_ptr(), out.data_ptr(), B, Cn)))
+    prog.ops.append(_lib.op_of("FRIDO_OP_FOLD", geo.fold_desc(moved.data_ptr(), out.data_ptr(), B, Cn)))
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):

@@ -1,6 +1,6 @@
 """CPU-side checks of DDIM inversion (DDIMSampler.invert): the coefficient table against its float64 formulas, the row's exact-inverse
 property, the round trip on an analytic Gaussian data model, the launcher in the header and in both builds, its argument checks (no device
-is touched), the unchanged ABI 7 layout and every refusal of `invert` with its name."""
+is touched), its op kind in ABI 8 and every refusal of `invert` with its name."""
 import ctypes as C
 
 import numpy as np
@@ -113,23 +113,24 @@ def test_round_trip_error_on_the_gaussian_model_falls_with_the_step_count():
 
 
 # ---- 3. the launcher and the ABI ------------------------------------------------------------------------------------------------------
-def test_header_declares_the_launcher_and_abi_7_is_untouched():
+def test_header_declares_the_launcher_and_its_op_kind():
     assert "frido_invert_step" in _lib.declared_symbols() and "frido_invert_step" in _lib.EXPORTS
-    assert _lib.ABI_VERSION == 7
-    assert _lib.OP_KINDS["FRIDO_OP__COUNT"] == 27 and _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == 26
+    assert _lib.ABI_VERSION == 8
+    assert _lib.OP_KINDS["FRIDO_OP__COUNT"] == 36 and _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == 26
     assert C.sizeof(_lib.FridoOp) == 520 and C.sizeof(_lib.STRUCTS["FridoSamplerStep"]) == 232
     assert C.sizeof(_lib.STRUCTS["FridoDpmStep"]) == 112 and C.sizeof(_lib.STRUCTS["FridoKeepBlend"]) == 120
-    assert "FridoInvertStep" in _lib.STRUCTS and "FridoInvertStep" not in _lib.KIND_STRUCT.values()      # a launcher of its own, not an op kind
-    assert C.sizeof(_lib.STRUCTS["FridoInvertStep"]) == 80 and _lib.DESC_INVERT_STEP == 1002 and _lib.DESC_KEEP_BLEND == 1001
-    assert patching.FOREIGN[runtime.INVERT_STEP] == "frido_invert_step"
+    assert _lib.OP_KINDS["FRIDO_OP_INVERT_STEP"] == 34 and _lib.KIND_STRUCT["FRIDO_OP_INVERT_STEP"] == "FridoInvertStep"
+    assert _lib.OP_KINDS["FRIDO_OP_KEEP_BLEND"] == 33 and _lib.KIND_STRUCT["FRIDO_OP_KEEP_BLEND"] == "FridoKeepBlend"
+    assert C.sizeof(_lib.STRUCTS["FridoInvertStep"]) == 80
 
 
 @pytest.mark.parametrize("planes", ["f16", "bf16"])
 def test_both_builds_export_the_launcher_and_agree_on_the_struct_size(planes):
     L = _lib.lib(planes)
     assert hasattr(L, "frido_invert_step")
-    assert L.frido_sizeof_desc(1002) == C.sizeof(_lib.STRUCTS["FridoInvertStep"])
-    assert L.frido_abi_version() == 7
+    assert L.frido_sizeof_desc(_lib.OP_KINDS["FRIDO_OP_INVERT_STEP"]) == L.frido_sizeof_desc(34) == C.sizeof(_lib.STRUCTS["FridoInvertStep"])
+    assert L.frido_sizeof_desc(1002) == -1      # the kind-less descriptor code of ABI 7 is gone
+    assert L.frido_abi_version() == 8
 
 
 I_OK = dict(x=0x1000, eps_cond=0x2000, eps_uncond=0x3000, cfg_dev=0x4000, coef=0x5000, step=0x6000, B=3, HW=35, Cx=9, c_lo=3, c_hi=6,

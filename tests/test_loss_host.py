@@ -1,6 +1,6 @@
 """CPU-side checks of the diffusion objective (FridoDiffusion.forward / p_losses / validation_step): lvlb_weights and the host helpers against
 the reference's own tensors (loss_host.npz), the constructor options and state_dict keys, the two launchers in the header and in both
-builds, their argument checks (no device is touched), the unchanged ABI 7 layout, and every refusal with its name."""
+builds, their argument checks (no device is touched), their op kinds in ABI 8, and every refusal with its name."""
 import ctypes as C
 
 import numpy as np
@@ -89,15 +89,21 @@ def test_state_dict_keys_change_only_by_logvar_under_learn_logvar():
         assert {k for k in keys if k.startswith(prefix + ".")} == {f"{prefix}.{k}" for k in module.state_dict()}
 
 
-def test_header_declares_both_launchers_and_abi_7_is_untouched():
+def test_header_declares_both_launchers_and_their_op_kinds():
     declared = _lib.declared_symbols()
     for name in ("frido_qsample", "frido_diffusion_loss"):
         assert name in declared and name in _lib.EXPORTS, name
-    assert _lib.ABI_VERSION == 7
-    assert _lib.OP_KINDS["FRIDO_OP__COUNT"] == 27 and _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == 26
+    assert _lib.ABI_VERSION == 8
+    assert _lib.OP_KINDS["FRIDO_OP__COUNT"] == 36 and _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == 26
     assert C.sizeof(_lib.FridoOp) == 520 and C.sizeof(_lib.STRUCTS["FridoGemm"]) == 512
     assert C.sizeof(_lib.STRUCTS["FridoSamplerStep"]) == 232
-    assert not any(k in _lib.KIND_STRUCT.values() for k in ("FridoQSample", "FridoDiffusionLoss"))      # launchers of their own, not op kinds
+    assert _lib.OP_KINDS["FRIDO_OP_QSAMPLE"] == 29 and _lib.KIND_STRUCT["FRIDO_OP_QSAMPLE"] == "FridoQSample"
+    assert _lib.OP_KINDS["FRIDO_OP_DIFFUSION_LOSS"] == 30 and _lib.KIND_STRUCT["FRIDO_OP_DIFFUSION_LOSS"] == "FridoDiffusionLoss"
+    for planes in ("f16", "bf16"):
+        L = _lib.lib(planes)
+        assert L.frido_abi_version() == 8
+        assert L.frido_sizeof_desc(29) == C.sizeof(_lib.STRUCTS["FridoQSample"]) and hasattr(L, "frido_qsample")
+        assert L.frido_sizeof_desc(30) == C.sizeof(_lib.STRUCTS["FridoDiffusionLoss"]) and hasattr(L, "frido_diffusion_loss")
     assert C.sizeof(_lib.STRUCTS["FridoQSample"]) == 112 and C.sizeof(_lib.STRUCTS["FridoDiffusionLoss"]) == 120
 
 
@@ -145,10 +151,12 @@ def test_null_descriptors_are_rejected():
     assert L.frido_diffusion_loss(None, None) == -1 and b"frido_diffusion_loss" in L.frido_last_error()
 
 
-def test_objective_launchers_are_registered_for_captured_programs():
-    from frido_amd import objective, patching
-    assert patching.FOREIGN[objective.QSAMPLE] == "frido_qsample" and patching.FOREIGN[objective.LOSS] == "frido_diffusion_loss"
-    assert patching.FOREIGN[patching.UNFOLD] == "frido_unfold" and patching.FOREIGN[patching.FOLD] == "frido_fold"
+def test_objective_launchers_are_op_kinds_for_captured_programs():
+    d = _lib.STRUCTS["FridoQSample"](**Q_OK)
+    assert _lib.op_of("FRIDO_OP_QSAMPLE", d) == (29, d) and _lib.op_of("FRIDO_OP_DIFFUSION_LOSS", _lib.STRUCTS["FridoDiffusionLoss"](**L_OK))[0] == 30
+    assert _lib.make_op("FRIDO_OP_UNFOLD")[0] == 27 and _lib.make_op("FRIDO_OP_FOLD")[0] == 28
+    with pytest.raises(TypeError, match="FRIDO_OP_DIFFUSION_LOSS takes a FridoDiffusionLoss"):
+        _lib.op_of("FRIDO_OP_DIFFUSION_LOSS", d)
 
 
 # ---- refusals: by name, never ignored -------------------------------------------------------------------------------------------------

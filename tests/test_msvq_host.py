@@ -1,6 +1,6 @@
 """CPU-side checks of MSFPNVQModel (the MS-VQGAN as a model of its own, taming/models/msvqgan.py:16-318): the three shipped msvqgan
 configs instantiate, the state_dict key set is the reference's (msvq_small.npz), every refusal says its name, CPU tensors raise, the
-codebook-loss launcher is declared / exported by both builds and rejects bad descriptors without touching a device, ABI 7 is untouched."""
+codebook-loss launcher is declared / exported by both builds and rejects bad descriptors without touching a device, its op kind in ABI 8."""
 import ctypes as C
 import json
 import os
@@ -122,12 +122,16 @@ def test_more_than_three_input_channels_are_refused(model):
 
 
 # ---- the launcher -----------------------------------------------------------------------------------------------------------------------
-def test_header_declares_the_launcher_and_abi_7_is_untouched():
+def test_header_declares_the_launcher_and_its_op_kind():
     assert "frido_vq_commit_loss" in _lib.declared_symbols() and "frido_vq_commit_loss" in _lib.EXPORTS
-    assert _lib.ABI_VERSION == 7
-    assert _lib.OP_KINDS["FRIDO_OP__COUNT"] == 27 and _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == 26
+    assert _lib.ABI_VERSION == 8
+    assert _lib.OP_KINDS["FRIDO_OP__COUNT"] == 36 and _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == 26
     assert C.sizeof(_lib.FridoOp) == 520 and C.sizeof(_lib.STRUCTS["FridoGemm"]) == 512 and C.sizeof(_lib.STRUCTS["FridoVq"]) == 80
-    assert "FridoVqCommitLoss" not in _lib.KIND_STRUCT.values()      # a launcher of its own, not an op kind
+    assert _lib.OP_KINDS["FRIDO_OP_VQ_COMMIT_LOSS"] == 31 and _lib.KIND_STRUCT["FRIDO_OP_VQ_COMMIT_LOSS"] == "FridoVqCommitLoss"
+    for planes in ("f16", "bf16"):
+        L = _lib.lib(planes)
+        assert L.frido_abi_version() == 8
+        assert L.frido_sizeof_desc(31) == C.sizeof(_lib.STRUCTS["FridoVqCommitLoss"]) and hasattr(L, "frido_vq_commit_loss")
     assert C.sizeof(_lib.STRUCTS["FridoVqCommitLoss"]) == 184
     assert _lib.VQLOSS_MAX_SCALES == 4 and _lib.VQLOSS_WS_BYTES == 4 * 256 * 8
 
@@ -137,9 +141,9 @@ def test_both_builds_export_the_launcher():
         assert hasattr(_lib.lib(planes), "frido_vq_commit_loss"), planes
 
 
-def test_launcher_is_registered_for_captured_programs():
-    from frido_amd import patching, vqloss
-    assert patching.FOREIGN[vqloss.VQLOSS] == "frido_vq_commit_loss"
+def test_launcher_is_an_op_kind_for_captured_programs():
+    d = _desc()
+    assert _lib.op_of("FRIDO_OP_VQ_COMMIT_LOSS", d) == (31, d)
 
 
 def _desc(n=2, **over):

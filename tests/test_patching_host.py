@@ -1,6 +1,6 @@
 """CPU-side checks of the patch-wise mode (FridoDiffusion.split_input_params): the weighting / normalization tables against the reference's
 own tensors (patch_apply.npz, patch_vq.npz), the crop grid and the clamping rules, every refusal with its message, the new launchers in the
-header, the launchers' argument checks (no device is touched) and the unchanged ABI 7 layout."""
+header, the launchers' argument checks (no device is touched) and their op kinds in ABI 8."""
 import ctypes as C
 
 import numpy as np
@@ -160,15 +160,21 @@ def test_patch_distributed_vq_false_leaves_the_first_stage_whole():
     assert "original_image_size" not in m.split_input_params
 
 
-def test_header_declares_the_new_launchers_and_abi_7_is_untouched():
+def test_header_declares_the_new_launchers_and_their_op_kinds():
     declared = _lib.declared_symbols()
     for name in ("frido_unfold", "frido_fold", "frido_capture_begin", "frido_capture_end"):
         assert name in declared and name in _lib.EXPORTS, name
-    assert _lib.ABI_VERSION == 7
-    assert _lib.OP_KINDS["FRIDO_OP__COUNT"] == 27 and _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == 26
+    assert _lib.ABI_VERSION == 8
+    assert _lib.OP_KINDS["FRIDO_OP__COUNT"] == 36 and _lib.OP_KINDS["FRIDO_OP_ATTN_MH"] == 26
     assert C.sizeof(_lib.FridoOp) == 520
     assert C.sizeof(_lib.STRUCTS["FridoSamplerStep"]) == 232
-    assert not any(k in _lib.KIND_STRUCT.values() for k in ("FridoUnfold", "FridoFold"))      # launchers of their own, not op kinds
+    assert _lib.OP_KINDS["FRIDO_OP_UNFOLD"] == 27 and _lib.KIND_STRUCT["FRIDO_OP_UNFOLD"] == "FridoUnfold"
+    assert _lib.OP_KINDS["FRIDO_OP_FOLD"] == 28 and _lib.KIND_STRUCT["FRIDO_OP_FOLD"] == "FridoFold"
+    for planes in ("f16", "bf16"):
+        L = _lib.lib(planes)
+        assert L.frido_abi_version() == 8
+        assert L.frido_sizeof_desc(27) == C.sizeof(_lib.STRUCTS["FridoUnfold"]) and hasattr(L, "frido_unfold")
+        assert L.frido_sizeof_desc(28) == C.sizeof(_lib.STRUCTS["FridoFold"]) and hasattr(L, "frido_fold")
     assert C.sizeof(_lib.STRUCTS["FridoUnfold"]) == 48 and C.sizeof(_lib.STRUCTS["FridoFold"]) == 80
 
 

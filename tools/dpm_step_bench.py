@@ -81,7 +81,8 @@ def main():
     for name, eng in engines.items():
         HW, Cn, nch = eng.H * eng.W, eng.C, eng.embed[s]
         if name == "dpm_2m":
-            desc = eng._update_op(s)[1]
+            kind, fields = eng._update_op(s)
+            desc = _lib.make_op(kind, **fields)[1]
             desc.x_out = scratch.data_ptr()
             L = _lib.lib(eng.planes)
             run = lambda: [_lib.check(L.frido_dpm_step(C.byref(desc), st.cuda_stream), "frido_dpm_step") for _ in range(n)]

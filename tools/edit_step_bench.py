@@ -86,8 +86,9 @@ def main():
     HW, a0, e0 = eng.H * eng.W, sum(eng.embed[:s]), sum(eng.embed[:s + 1])
     L = _lib.lib(eng.planes)
     eng.step.zero_()
-    for label, desc, nbytes in (("masked Philox blend", eng._blend_op(s, (a0, e0), True)[1], B * HW * (3 * (e0 - a0) + 1) * 4),
-                                ("clean blend (reimpose)", eng._blend_op(s, (a0, e0), True, clean=True)[1], B * HW * (3 * (e0 - a0) + 1) * 4)):
+    blend = lambda **kw: _lib.make_op("FRIDO_OP_KEEP_BLEND", **eng._blend_op(s, (a0, e0), True, **kw)[1])[1]
+    for label, desc, nbytes in (("masked Philox blend", blend(), B * HW * (3 * (e0 - a0) + 1) * 4),
+                                ("clean blend (reimpose)", blend(clean=True), B * HW * (3 * (e0 - a0) + 1) * 4)):
         run = lambda: [_lib.check(L.frido_keep_blend(C.byref(desc), st.cuda_stream), "frido_keep_blend") for _ in range(n)]
         run()
         torch.cuda.synchronize()

@@ -81,7 +81,8 @@ def main():
     nch = eng.embed[s]
     L = _lib.lib(eng.planes)
     eng.step.zero_()
-    desc = eng._update_op(s)[1]
+    kind, fields = eng._update_op(s)
+    desc = _lib.make_op(kind, **fields)[1]
     nbytes = B * eng.H * eng.W * 3 * nch * 4       # reads x and eps, writes x, on the window
     run = lambda: [_lib.check(L.frido_invert_step(C.byref(desc), st.cuda_stream), "frido_invert_step") for _ in range(n)]
     run()
