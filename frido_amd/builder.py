@@ -546,10 +546,12 @@ class Builder:
                        x_bf16=int(getattr(x, "bf16", False)))
         return a
 
-    def softmax(self, s, rows, N, ld, Npad):
+    def softmax(self, s, rows, N, ld, Npad, causal_nq=0):
+        """Row softmax of the f32 scores s [rows][ld] -> operand [rows][Npad], zero beyond N.  causal_nq > 0: row r sees keys
+        0 .. (r mod causal_nq) only (FridoSoftmax.causal_nq: the CLIP text tower's mask)."""
         p = self.op(rows, Npad)
         self.prog.emit("FRIDO_OP_SOFTMAX", x=s.ptr, rows=rows, N=N, ld=ld, Npad=Npad, nsplit=self.nsplit, out_op=p.ptr,
-                       out_lo=p.lo)
+                       out_lo=p.lo, causal_nq=causal_nq)
         return p
 
     def geglu(self, g, H):

@@ -47,9 +47,7 @@ class ClipTextPlan:
             prog.gemm(n, n, dh, qk, (qk.ptr + 2 * width, qk.lo), batch=B * H, batch_inner=H, lda=2 * width, ldb=2 * width,
                       a_bs=n * 2 * width, a_bs2=dh, b_bs=n * 2 * width, b_bs2=dh, alpha=float(dh) ** -0.5,
                       out_f32=s.ptr, of_bs=H * n * n, of_bs2=n * n, ldo=n)
-            pr = b.op(B * H * n, Np)
-            prog.emit("FRIDO_OP_SOFTMAX", x=s.ptr, rows=B * H * n, N=n, ld=n, Npad=Np, nsplit=b.nsplit, out_op=pr.ptr, out_lo=pr.lo,
-                      causal_nq=n)
+            pr = b.softmax(s, B * H * n, n, n, Np, causal_nq=n)
             s.free()
             o = b.op(B * n, width)
             prog.gemm(n, dh, Np, pr, vT, batch=B * H, batch_inner=H, lda=Np, ldb=Np, a_bs=H * n * Np, a_bs2=n * Np,
