@@ -30,8 +30,9 @@ class BertPlan:
             hn = b.layernorm(x, a + ".0")
             wqk = b.cat_lin_weight(("bert_qk", a), [a + ".1.to_q.weight", a + ".1.to_k.weight"])
             qk = b.op(B * n, 2 * inner)
-            b.linear(hn, None, wop=wqk, bias=False, out=("op", qk))
-            b.v_transposed(hn, dim, b.lin_weight(a + ".1.to_v.weight"), B, n, inner, out=vT)
+            with b.gemm_pair():      # two projections of the same rows, independent of each other
+                b.linear(hn, None, wop=wqk, bias=False, out=("op", qk))
+                b.v_transposed(hn, dim, b.lin_weight(a + ".1.to_v.weight"), B, n, inner, out=vT)
             hn.free()
             # scores[b][h] = q[b][:, h*dh:(h+1)*dh] @ k[b][:, h*dh:...]^T * dh^-0.5
             s = b.f32_strict(B * H * n, n)

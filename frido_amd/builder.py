@@ -16,6 +16,9 @@ ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2
 GN_FUSED_MAX_HW = 256   # test knob: one-launch GroupNorm (norm.hip gn_fused_kernel) up to this plane size; larger planes: gn_stats + gn_apply are faster
 # test knob (r04): a split-K GEMM whose output goes straight into a one-launch GroupNorm leaves its reduction to that launch (no splitk_reduce)
 SK_DEFER = True
+# test knob: the two independent projections of a self-attention block that read the same normalised rows (V^T and q' / qk / qkv) are
+# emitted as a pair (Prog.gemm_pair -> frido_gemm_pair: one grid where their tiles allow it).  Results are the same bit for bit.
+GEMM_PAIR = True
 # test knob: from this many keys on, the flash-style kernel (flash.hip).  Below it the score matrix is small and the batched
 # GEMM -> softmax -> GEMM chain fills the chip better than one workgroup per 64 queries (measured at B = 16: 256 keys x d = 576:
 # 37 us vs 49 us; 1024 keys x d = 384: 102 vs 82 us)
@@ -48,6 +51,15 @@ class Builder:
             yield mine
         finally:
             self._persist = outer
+
+    @contextlib.contextmanager
+    def gemm_pair(self):
+        """Bracket of the two independent GEMMs of a pair (Prog.gemm_pair), a plain scope with GEMM_PAIR off."""
+        if GEMM_PAIR:
+            with self.prog.gemm_pair():
+                yield
+        else:
+            yield
 
     # ---- programs ------------------------------------------------------------------------------
     def new_prog(self):

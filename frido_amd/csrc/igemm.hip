@@ -22,6 +22,7 @@
 //    registers -- see tile_epilogue;
 //  * the BK = 64 bf16 tiles run a software-pipelined loop (fragments of the next k-step prefetched under the MFMAs);
 //  * split-K work items (k-slice, tile) are dealt to the XCDs in contiguous ranges (xcd_item).
+#ifndef IGEMM_BODY_PASS      // (set while this file includes itself for the ring kernel's body alone: see igemm_kernel)
 #include "igemm_shared.h"
 #include <atomic>
 
@@ -106,8 +107,17 @@ __device__ __forceinline__ void wait_tail(int rem) {
     }
 }
 
+// The body below is TEXT shared by igemm_kernel and igemm_pair_kernel: the latter includes this file once more with IGEMM_BODY_PASS set,
+// which leaves only the lines between the two IGEMM_BODY_PASS brackets.  It expects in scope: BM, BN, NS, CONV, BK, W8, KG; `d` (const
+// FridoGemm&); `vg`, the block coordinates / grid dimensions it works in (HwGrid or VGrid, igemm_shared.h); `PAIR` (no start stagger, and
+// with gz() == 1 no split-K).  Not a __forceinline__ function: as one the body is optimised on its own before it is inlined (its descriptor
+// an opaque reference) and 43 of the 53 igemm_kernel instantiations came out with other register counts; as text all 53 compile to the
+// instruction sequence they had before the pair kernel existed (profiles/gemm_pair_isa.txt).
 template <int BM, int BN, int NS, bool CONV, int BK, bool W8 = false, int KG = 1>
 __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS, BK, W8, KG>::NW == 8 || KG == 2) ? 1 : 2)) void igemm_kernel(const FridoGemm d) {
+    constexpr bool PAIR = false;
+    const HwGrid vg{};
+#endif  // IGEMM_BODY_PASS
     using G = Geo<BM, BN, NS, BK, W8, KG>;
 #if IG_PROF
     unsigned igp[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
@@ -138,8 +148,8 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
     // split-K an XCD works on ONE k-slice (or a few), so its L2 holds that slice of the weights once.  Before (k-slice =
     // blockIdx.z, every XCD walked all slices): the 8x8-plane convs (M = 1024, split 8) fetched 72 MB per launch from
     // MALL / HBM for 18.6 MB of operands (tools/_pmc_smallm.sh).
-    const int kz = xcd_item(nb) / nb;                          // (KG = 2 launches have gridDim.z == 1: kz = 0)
-    const int bid = xcd_item(nb) - kz * nb;
+    const int kz = xcd_item(nb, vg) / nb;                      // (KG = 2 launches have gridDim.z == 1: kz = 0)
+    const int bid = xcd_item(nb, vg) - kz * nb;
     int tm = bid / tiles_n, tn = bid - tm * tiles_n;
     // (r06) COLUMN PANELS (FridoGemm.flags bit 27): with many tile columns an XCD's 64 concurrent workgroups cover a few tile rows x ALL
     // columns, i.e. the whole weight matrix -- beyond its 4-MB L2 (GEGLU projection 16384 x 3072 x 384: 4.7 MB of weights + the rows'
@@ -166,8 +176,8 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
         }
     }
     const int m0 = tm * BM, n0 = tn * BN;
-    if constexpr (NW == 4) {
-        const int id = ((int)blockIdx.y * (int)gridDim.z + (int)blockIdx.z) * (int)gridDim.x + (int)blockIdx.x;
+    if constexpr (NW == 4 && !PAIR) {
+        const int id = ((int)vg.by() * (int)vg.gz() + (int)vg.bz()) * (int)vg.gx() + (int)vg.bx();
         // delay in QUARTER microseconds (a k-step of these tiles is ~1 us: sub-k-step offsets are the interesting ones for
         // one-round launches), smallest grid in units of 64 workgroups, and which workgroups wait: mode 0 = dispatch ids 256..511 (the
         // second slot of every CU if the dispatcher deals one workgroup per CU first), mode 1 = every other workgroup of an XCD among
@@ -176,17 +186,17 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
         const int min_wg = ((d.flags >> 16) & 255) ? ((d.flags >> 16) & 255) * 64 : 768;
         const int mode = (d.flags >> 24) & 3;
         const bool late = mode == 0 ? (id >= 256 && id < 512) : (id < 512 && ((id >> 3) & 1));
-        if (ticks && late && (int)(gridDim.x * gridDim.y * gridDim.z) >= min_wg) {
+        if (ticks && late && (int)(vg.gx() * vg.gy() * vg.gz()) >= min_wg) {
             const uint64_t t0 = wall_clock64();
             while (wall_clock64() - t0 < (uint64_t)ticks) __builtin_amdgcn_s_sleep(4);
         }
     }
-    if constexpr (NW == 8) stagger_one_per_cu(d.flags);
+    if constexpr (NW == 8 && !PAIR) stagger_one_per_cu(d.flags);
     // batch index, optionally two-level (outer x inner, e.g. image x head)
-    int zo = blockIdx.y, zi = 0;
+    int zo = vg.by(), zi = 0;
     if (d.batch_inner > 1) {
-        zo = blockIdx.y / d.batch_inner;
-        zi = blockIdx.y - zo * d.batch_inner;
+        zo = vg.by() / d.batch_inner;
+        zi = vg.by() - zo * d.batch_inner;
     }
     const frido_bf16* __restrict__ Ab = d.A + (int64_t)zo * d.a_bs + (int64_t)zi * d.a_bs2;
     const frido_bf16* __restrict__ Bb = d.B + (int64_t)zo * d.b_bs + (int64_t)zi * d.b_bs2;
@@ -245,7 +255,7 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
     const int nk_all = (d.K + d.K2) / BK;
     // (KG = 2: the two groups of the workgroup are the two "slices"; the launcher admits an even number of k-tiles only, so both
     //  groups run the same number of loop iterations and meet at the same workgroup-wide barriers)
-    const int per = KG == 2 ? nk_all / 2 : (nk_all + (int)gridDim.z - 1) / (int)gridDim.z;
+    const int per = KG == 2 ? nk_all / 2 : (nk_all + (int)vg.gz() - 1) / (int)vg.gz();
     const int kt0 = (KG == 2 ? kg : kz) * per;
     const int nk = max(0, min(nk_all, kt0 + per) - kt0);
     const int cin = d.Cin, kw = d.kw, ws = d.Ws;
@@ -745,9 +755,9 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
 #pragma unroll
             for (int j = 0; j < TN; ++j) acc[i][j] += *reinterpret_cast<const f32x4*>(red + (i * TN + j) * 1024);
     }
-    if (KG == 1 && gridDim.z > 1 && d.sk_mode == 1) {
+    if (KG == 1 && vg.gz() > 1 && d.sk_mode == 1) {
         constexpr int NT = G::NT, SLAB = BM * BN;
-        const int S = (int)gridDim.z;
+        const int S = (int)vg.gz();
         float* part = d.ws + SK_HDR + (int64_t)bid * S * SLAB;
         {
             float* mine = part + (int64_t)kz * SLAB + t * 4;
@@ -805,7 +815,7 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the stores have left the wave (not: reached memory)
     igp[5] = IGP_NOW() - igp_prev;
     {
-        const int wg = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
+        const int wg = PAIR ? (int)blockIdx.x : (int)(vg.bx() + vg.gx() * (vg.by() + vg.gy() * vg.bz()));
         if (lane == 0 && wg < 4096 && wave < 8) {
             unsigned* o = g_ig_prof + (wg * 8 + wave) * 8;
 #pragma unroll
@@ -813,6 +823,36 @@ __global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, KG>::NT), ((Geo<BM, BN, NS
         }
     }
 #endif
+#ifndef IGEMM_BODY_PASS
+}
+
+// Pair launch (frido_gemm_pair): TWO dense GEMMs of the same tile program in ONE 1-D grid, so that one member's prologue and store drain
+// run under the other member's k-loop where a member alone is a single sub-round launch.  Workgroups [0, nblk0p) belong to member 0 --
+// nblk0p = its tiles x batch rounded up to a multiple of 8, so that member 1 keeps its XCD phase; the surplus workgroups return at once --
+// the rest to member 1.  A workgroup decodes (x, y, z = 0) in its member's own (tiles, batch, 1) space and runs the unchanged body on
+// that member's descriptor: every output is bit for bit what the member's single launch writes.  Both descriptors travel as kernel
+// arguments (the selected one is read through a pointer into the kernarg segment: nothing is fetched ahead of the first DMA).
+template <int BM, int BN, int NS, int BK, bool W8 = false>
+__global__ __launch_bounds__((Geo<BM, BN, NS, BK, W8, 1>::NT), (Geo<BM, BN, NS, BK, W8, 1>::NW == 8 ? 1 : 2)) void igemm_pair_kernel(
+    const FridoGemm d0, const FridoGemm d1, int nblk0p) {
+    static_assert(sizeof(FridoGemm) == 512 && alignof(FridoGemm) <= 8, "kernarg layout: d0 at 0, d1 at 512, nblk0p at 1024");
+    const bool second = (int)blockIdx.x >= nblk0p;              // workgroup-uniform
+    // the member's descriptor is read where it lies in the kernarg segment.  (`second ? d1 : d0` made hipcc load BOTH descriptors and
+    // select field by field -- ~100 spilled SGPRs -- or copy one to scratch; the opaque offset keeps it to one set of scalar loads.)
+    int off = second ? (int)sizeof(FridoGemm) : 0;
+    asm volatile("" : "+s"(off));
+    typedef const __attribute__((address_space(4))) char* kptr_t;
+    const FridoGemm& d = *(const FridoGemm*)((kptr_t)__builtin_amdgcn_kernarg_segment_ptr() + off);
+    const int id = second ? (int)blockIdx.x - nblk0p : (int)blockIdx.x;
+    const int tiles = ((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
+    const int y = id / tiles;
+    if (y >= d.batch) return;                                   // member 0's rounding surplus
+    constexpr bool CONV = false, PAIR = true;
+    constexpr int KG = 1;
+    const VGrid vg{(unsigned)(id - y * tiles), (unsigned)y, (unsigned)tiles, (unsigned)d.batch};
+#define IGEMM_BODY_PASS
+#include "igemm.hip"
+#undef IGEMM_BODY_PASS
 }
 
 #if IG_PROF
@@ -1608,6 +1648,102 @@ int pick_tile(const FridoGemm& d) {
     return 3;
 }
 
+// ---- pair launch (igemm_pair_kernel) ----
+// Ring-kernel instantiation a dense descriptor's tile resolves to, exactly as dispatch_tile<NS, false> resolves it, as
+// (BM << 16) | (BN << 4) | (BK == 64) << 1 | W8 -- or -1 where the launch is not one plain ring-kernel grid (a conv, split-K, a fused
+// GroupNorm input, a tile outside 1..8 / 11..19).
+int pair_inst(const FridoGemm& d) {
+    if (d.conv || d.splitk > 1 || d.gn_x1) return -1;
+    const int tile = d.tile ? d.tile : pick_tile(d);
+    auto id = [](int bm, int bn, int k64, int w8) { return (bm << 16) | (bn << 4) | (k64 << 1) | w8; };
+    if (!((tile >= 1 && tile <= 8) || (tile >= 11 && tile <= 19))) return -1;
+    switch (tile) {
+        case 1: return id(128, 128, 0, 0);
+        case 2: return id(128, 192, 0, 0);
+        case 4: return id(128, 64, 0, 0);
+        case 5: return id(64, 192, 0, 0);
+        case 6: return id(64, 128, 0, 0);
+        case 7: return id(256, 128, 0, 0);
+        default: break;
+    }
+    if (d.nsplit == 2) {
+        if (tile == 18) return id(128, 192, 0, 1);
+        if (tile == 19) return id(256, 192, 0, 0);
+    }
+    if (d.nsplit == 1) {
+        if (tile == 8) return id(256, 256, 0, 0);
+        if ((d.K & 63) == 0 && (d.K2 & 63) == 0) switch (tile) {
+            case 11: return id(128, 128, 1, 0);
+            case 12: return id(128, 192, 1, 0);
+            case 13: return id(64, 64, 1, 0);
+            case 14: return id(128, 64, 1, 0);
+            case 15: return id(64, 192, 1, 0);
+            case 16: return id(64, 128, 1, 0);
+            case 17: return id(256, 128, 1, 0);
+            default: break;
+        }
+    }
+    return id(64, 64, 0, 0);
+}
+
+template <int BM, int BN, int NS, int BK, bool W8 = false>
+int set_attr_pair() {
+    constexpr int smem = Geo<BM, BN, NS, BK, W8>::SMEM;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_pair_kernel<BM, BN, NS, BK, W8>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            smem) != hipSuccess) {
+        frido_set_error("igemm: cannot set dynamic LDS size %d (pair kernel)", smem);
+        return FRIDO_EHIP;
+    }
+    return FRIDO_OK;
+}
+
+template <int BM, int BN, int NS, int BK, bool W8 = false>
+int launch_pair(const FridoGemm& a, const FridoGemm& b, hipStream_t s) {
+    using G = Geo<BM, BN, NS, BK, W8>;
+    auto blocks = [](const FridoGemm& d) { return (int64_t)((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN) * d.batch; };
+    const int64_t n0p = (blocks(a) + 7) / 8 * 8, n1 = blocks(b);
+    if (n0p + n1 > 0x7fffffff) {
+        frido_set_error("igemm: a pair launch of %lld workgroups", (long long)(n0p + n1));
+        return FRIDO_EINVAL;
+    }
+    FridoGemm da = a, db = b;           // (as launch(): no split-K, so sk_mode means nothing)
+    da.sk_mode = 0;
+    db.sk_mode = 0;
+    hipLaunchKernelGGL((igemm_pair_kernel<BM, BN, NS, BK, W8>), dim3((unsigned)(n0p + n1)), dim3(G::NT), G::SMEM, s, da, db, (int)n0p);
+    return frido_check_launch("igemm (pair)");
+}
+
+template <int NS>
+int dispatch_pair(int inst, const FridoGemm& a, const FridoGemm& b, hipStream_t s) {
+    const int bm = inst >> 16, bn = (inst >> 4) & 0xfff, k64 = (inst >> 1) & 1, w8 = inst & 1;
+#define FRIDO_PAIR(BM, BN, BK, W8) if (bm == BM && bn == BN && k64 == (BK == 64) && w8 == (int)W8) return launch_pair<BM, BN, NS, BK, W8>(a, b, s)
+    FRIDO_PAIR(64, 64, 32, false); FRIDO_PAIR(128, 128, 32, false); FRIDO_PAIR(128, 192, 32, false); FRIDO_PAIR(128, 64, 32, false);
+    FRIDO_PAIR(64, 192, 32, false); FRIDO_PAIR(64, 128, 32, false); FRIDO_PAIR(256, 128, 32, false);
+    if constexpr (NS == 2) {
+        FRIDO_PAIR(128, 192, 32, true); FRIDO_PAIR(256, 192, 32, false);
+    } else {
+        FRIDO_PAIR(256, 256, 32, false);
+        FRIDO_PAIR(64, 64, 64, false); FRIDO_PAIR(128, 128, 64, false); FRIDO_PAIR(128, 192, 64, false); FRIDO_PAIR(128, 64, 64, false);
+        FRIDO_PAIR(64, 192, 64, false); FRIDO_PAIR(64, 128, 64, false); FRIDO_PAIR(256, 128, 64, false);
+    }
+#undef FRIDO_PAIR
+    frido_set_error("igemm: no pair kernel for instantiation %#x", inst);
+    return FRIDO_EINVAL;
+}
+
+template <int NS>
+int set_attr_pairs() {
+    int rc = set_attr_pair<64, 64, NS, 32>() | set_attr_pair<128, 128, NS, 32>() | set_attr_pair<128, 192, NS, 32>() | set_attr_pair<128, 64, NS, 32>() |
+             set_attr_pair<64, 192, NS, 32>() | set_attr_pair<64, 128, NS, 32>() | set_attr_pair<256, 128, NS, 32>();
+    if constexpr (NS == 2) {
+        rc |= set_attr_pair<128, 192, NS, 32, true>() | set_attr_pair<256, 192, NS, 32>();
+    } else {
+        rc |= set_attr_pair<256, 256, NS, 32>() | set_attr_pair<64, 64, NS, 64>() | set_attr_pair<128, 128, NS, 64>() | set_attr_pair<128, 192, NS, 64>() |
+              set_attr_pair<128, 64, NS, 64>() | set_attr_pair<64, 192, NS, 64>() | set_attr_pair<64, 128, NS, 64>() | set_attr_pair<256, 128, NS, 64>();
+    }
+    return rc;
+}
+
 }  // namespace
 
 int frido_igemm_init() {
@@ -1625,6 +1761,7 @@ int frido_igemm_init() {
     rc |= set_attr<256, 192, 2, true, 32>() | set_attr<256, 192, 2, false, 32>();
     rc |= set_attr<256, 128, 1, true, 32>() | set_attr<256, 128, 1, false, 32>() | set_attr<256, 256, 1, true, 32>() |
           set_attr<256, 256, 1, false, 32>() | set_attr<256, 128, 1, true, 64>() | set_attr<256, 128, 1, false, 64>();
+    rc |= set_attr_pairs<1>() | set_attr_pairs<2>();
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_patch_kernel<192, 8, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             PGeo<192, 8>::SMEM) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_patch_kernel<192, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1664,7 +1801,9 @@ extern "C" int64_t frido_gemm_workspace_bytes(const FridoGemm* d) {
     return (int64_t)SK_HDR * 4 + (int64_t)d->splitk * Mp * Np * (int64_t)sizeof(float);
 }
 
-extern "C" int frido_gemm(const FridoGemm* dp, frido_stream_t stream) {
+// argument checks of frido_gemm / frido_gemm_pair (its own namespace so that the messages keep naming frido_gemm)
+namespace gemm_args {
+static int frido_gemm(const FridoGemm* dp) {
     FRIDO_REQUIRE(dp != nullptr, "null descriptor");
     const FridoGemm& d = *dp;
     FRIDO_REQUIRE(d.M > 0 && d.N > 0 && d.K > 0 && d.batch > 0, "empty problem");
@@ -1719,9 +1858,36 @@ extern "C" int frido_gemm(const FridoGemm* dp, frido_stream_t stream) {
                           "sk_mode 2: plain f32 output [M][N] whose epilogue splitk_reduce8 could run (see frido_hip.h)");
         }
     }
-    if (const int arc = ensure_device_attrs()) return arc;
+    return FRIDO_OK;
+}
+}  // namespace gemm_args
+
+static int gemm_launch(const FridoGemm& d, frido_stream_t stream) {      // a checked descriptor -> its tile's kernel
     const int tile = d.tile ? d.tile : pick_tile(d);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (d.nsplit == 1) return d.conv ? dispatch_tile<1, true>(d, tile, s) : dispatch_tile<1, false>(d, tile, s);
     return d.conv ? dispatch_tile<2, true>(d, tile, s) : dispatch_tile<2, false>(d, tile, s);
 }
+
+extern "C" int frido_gemm(const FridoGemm* dp, frido_stream_t stream) {
+    if (const int rc = gemm_args::frido_gemm(dp)) return rc;
+    if (const int arc = ensure_device_attrs()) return arc;
+    return gemm_launch(*dp, stream);
+}
+
+// Two independent GEMMs as a drop-in for two frido_gemm calls (a first, then b).  Both descriptors are checked before anything is
+// launched.  ONE grid (igemm_pair_kernel) when both are dense, neither is split along K, their nsplit is the same and their tiles
+// resolve to the same ring-kernel instantiation (tiles 1..8, 11..19); otherwise the two launches one after the other.
+extern "C" int frido_gemm_pair(const FridoGemm* a, const FridoGemm* b, frido_stream_t stream) {
+    if (const int rc = gemm_args::frido_gemm(a)) return rc;
+    if (const int rc = gemm_args::frido_gemm(b)) return rc;
+    if (const int arc = ensure_device_attrs()) return arc;
+    const int inst = pair_inst(*a);
+    if (inst >= 0 && inst == pair_inst(*b) && a->nsplit == b->nsplit) {
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        return a->nsplit == 1 ? dispatch_pair<1>(inst, *a, *b, s) : dispatch_pair<2>(inst, *a, *b, s);
+    }
+    if (const int rc = gemm_launch(*a, stream)) return rc;
+    return gemm_launch(*b, stream);
+}
+#endif  // IGEMM_BODY_PASS

@@ -29,6 +29,34 @@ __device__ __forceinline__ int xcd_item(int nb) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
 }
 
+// Block coordinates and grid dimensions as the ring kernel's body sees them: the hardware's in a plain launch (HwGrid: every use reads
+// the builtin where it stands, so igemm_kernel compiles to what it was before the body became a function), a member's own
+// (tiles, batch, 1) space in a pair launch (VGrid; igemm_pair_kernel), where one 1-D grid carries the workgroups of two GEMMs.
+struct HwGrid {
+    __device__ __forceinline__ unsigned bx() const { return blockIdx.x; }
+    __device__ __forceinline__ unsigned by() const { return blockIdx.y; }
+    __device__ __forceinline__ unsigned bz() const { return blockIdx.z; }
+    __device__ __forceinline__ unsigned gx() const { return gridDim.x; }
+    __device__ __forceinline__ unsigned gy() const { return gridDim.y; }
+    __device__ __forceinline__ unsigned gz() const { return gridDim.z; }
+};
+struct VGrid {
+    unsigned x, y, nx, ny;
+    __device__ __forceinline__ unsigned bx() const { return x; }
+    __device__ __forceinline__ unsigned by() const { return y; }
+    __device__ __forceinline__ unsigned bz() const { return 0u; }
+    __device__ __forceinline__ unsigned gx() const { return nx; }
+    __device__ __forceinline__ unsigned gy() const { return ny; }
+    __device__ __forceinline__ unsigned gz() const { return 1u; }
+};
+template <class GRID>
+__device__ __forceinline__ int xcd_item(int nb, const GRID& g) {
+    const int total = nb * (int)g.gz();
+    const int id = (int)g.bz() * (int)g.gx() + (int)g.bx();
+    const int q = total >> 3, r = total & 7, xcd = id & 7, loc = id >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+}
+
 // Run-time start stagger of the ONE-workgroup-per-CU kernels (8-wave igemm tiles, the fused GroupNorm + conv kernel), which run a launch's
 // prologue loads, its k-loop and its epilogue stores chip-wide at the same time.  FridoGemm.flags bit 26 lets the odd XCDs (dispatch
 // id & 1) start bits 8..15 quarter microseconds late, so that one half's HBM phases fall under the other half's MFMA phase.  Results

@@ -124,9 +124,29 @@ int run_sync(const FridoSync& d, hipStream_t main) {
     return FRIDO_OK;
 }
 
+// FridoGemm.flags bit 28: op i is the head of a pair (frido_gemm_pair with op i + 1)
+constexpr int GEMM_PAIRED = 1 << 28;
+
+bool pair_head(const FridoOp& op) { return op.kind == FRIDO_OP_GEMM && (op.u.gemm.flags & GEMM_PAIRED); }
+
+// the head's partner must be the next op, a GEMM on the same stream; nothing is launched otherwise
+int pair_check(const FridoOp* ops, int32_t n, int32_t i) {
+    if (i + 1 >= n || ops[i + 1].kind != FRIDO_OP_GEMM || ops[i + 1].stream != ops[i].stream) {
+        frido_set_error("op %d (kind %d): a paired GEMM (flags bit 28) must be followed by a FRIDO_OP_GEMM on the same stream", i, ops[i].kind);
+        return FRIDO_EINVAL;
+    }
+    return FRIDO_OK;
+}
+
 int run_prog(const FridoOp* ops, int32_t n, frido_stream_t s) {
+    for (int32_t i = 0; i < n; ++i)       // a malformed pair fails the program before its first launch
+        if (pair_head(ops[i])) {
+            if (const int rc = pair_check(ops, n, i)) return rc;
+            ++i;                          // (the partner's own bit 28, if set, means nothing)
+        }
     for (int32_t i = 0; i < n; ++i) {
         int rc;
+        const int32_t i0 = i;
         if (ops[i].kind == FRIDO_OP_SYNC) {
             rc = run_sync(ops[i].u.sync, (hipStream_t)s);
         } else {
@@ -139,12 +159,17 @@ int run_prog(const FridoOp* ops, int32_t n, frido_stream_t s) {
                 }
                 st = (frido_stream_t)sd->stream;
             }
-            rc = run_one(ops[i], st);
+            if (pair_head(ops[i])) {
+                rc = frido_gemm_pair(&ops[i].u.gemm, &ops[i + 1].u.gemm, st);
+                ++i;
+            } else {
+                rc = run_one(ops[i], st);
+            }
         }
         if (rc != FRIDO_OK) {
             char tmp[400];
             snprintf(tmp, sizeof(tmp), "%s", g_err);
-            frido_set_error("op %d (kind %d): %s", i, ops[i].kind, tmp);
+            frido_set_error("op %d (kind %d): %s", i0, ops[i0].kind, tmp);
             return rc;
         }
     }
@@ -166,13 +191,24 @@ extern "C" int frido_run_timed(const FridoOp* ops, int32_t n, frido_stream_t s, 
         frido_set_error("frido_run_timed: bad arguments");
         return FRIDO_EINVAL;
     }
+    for (int32_t i = 0; i < n; ++i)
+        if (pair_head(ops[i])) {
+            if (const int rc = pair_check(ops, n, i)) return rc;
+            ++i;
+        }
     std::vector<hipEvent_t> ev(n + 1);
     for (auto& e : ev)
         if (hipEventCreate(&e) != hipSuccess) return FRIDO_EHIP;
     int rc = FRIDO_OK;
     (void)hipEventRecord(ev[0], (hipStream_t)s);
     for (int32_t i = 0; i < n && rc == FRIDO_OK; ++i) {
-        if (ops[i].kind != FRIDO_OP_SYNC) rc = run_one(ops[i], s);          // per-op timing: everything on the caller's stream
+        if (pair_head(ops[i])) {          // the pair's time is the head's; its partner reports 0
+            rc = frido_gemm_pair(&ops[i].u.gemm, &ops[i + 1].u.gemm, s);
+            (void)hipEventRecord(ev[i + 1], (hipStream_t)s);
+            ++i;
+        } else if (ops[i].kind != FRIDO_OP_SYNC) {
+            rc = run_one(ops[i], s);          // per-op timing: everything on the caller's stream
+        }
         (void)hipEventRecord(ev[i + 1], (hipStream_t)s);
     }
     if (rc == FRIDO_OK) {

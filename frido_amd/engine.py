@@ -25,6 +25,7 @@ STAGGER_US = float(os.environ.get("FRIDO_STAGGER_US", "12"))         # quarter-m
 STAGGER_MIN_WG = int(os.environ.get("FRIDO_STAGGER_MIN_WG", "0"))
 # (bits 24..27 -- the stagger control forms and the column-panel tile order, all measured and left off -- are reachable through FRIDO_GEMM_FLAGS only)
 GEMM_FLAGS |= ((int(round(STAGGER_US * 4)) & 255) << 8) | (((STAGGER_MIN_WG // 64) & 255) << 16)
+GEMM_PAIRED = 1 << 28    # FridoGemm.flags bit 28: this GEMM and the next op go to frido_gemm_pair (include/frido_hip.h)
 BF16X3 = 2   # nsplit: hi + residual plane, 3 MFMAs per product (≈ fp32 accuracy)
 BF16 = 1     # nsplit: plain bf16 operands
 
@@ -307,6 +308,34 @@ class Prog:
                 # ops of the executor's side stream run CONCURRENTLY with main-stream ops: they get their own workspace
                 st.ws = tune.workspace_for(st, self.device, self.ws_tag + (":s1" if self._sid else ""))
         self.flops += 2 * M * N * (K + K2) * batch * (3 if self.nsplit == 2 else 1)
+
+    @contextlib.contextmanager
+    def gemm_pair(self):
+        """The TWO GEMMs emitted inside are independent (neither reads what the other writes): the head op gets FridoGemm.flags bit 28
+        and the executor hands both to frido_gemm_pair -- one grid where both resolve to the same ring-kernel tile, the two launches
+        otherwise; bit for bit the outputs of the unflagged program either way.
+        Tiles: with the tuner off or FRIDO_TUNE_ON_MISS=static both members keep the tile they got.  With the tuner on, tune.best_pair
+        times the pair on every tile both members take against the members' own best launches back to back: where the pair wins, both
+        get its tile (and the faster member order); where it loses, the two stay unpaired."""
+        n0 = len(self.ops)
+        yield
+        kind = _lib.OP_KINDS["FRIDO_OP_GEMM"]
+        assert len(self.ops) == n0 + 2 and all(k == kind for k, _ in self.ops[n0:]), "gemm_pair brackets exactly two GEMMs"
+        a, b = self.ops[n0][1], self.ops[n0 + 1][1]
+        assert a._sid == b._sid
+        if self.device.type == "cuda":
+            from . import tune
+            choice = tune.best_pair(a, b, self.device)
+            if choice is not None:
+                tile, swap = choice
+                if not tile:
+                    return          # timed: the two single launches win
+                for st in (a, b):
+                    st.tile, st.splitk, st.ws = tile, 1, None
+                if swap:
+                    self.ops[n0], self.ops[n0 + 1] = self.ops[n0 + 1], self.ops[n0]
+        self.ops[n0][1].flags |= GEMM_PAIRED
+        self._packed = None
 
     # ---- execution ---------------------------------------------------------------------------
     def packed(self):

@@ -123,17 +123,9 @@ def signature(st):
     return sig
 
 
-def best_tile(st, device, stream):
-    """st: a filled FridoGemm ctypes struct (pointers are ignored: scratch buffers are substituted).
-    Returns (tile, splitk) -- or (tile, splitk, start delay in quarter microseconds) for a signature whose pinned cache entry carries
-    one (written by tools/tune_in_context.py --stagger; this function's own timing never produces the third element)."""
-    if not ENABLED:
-        return 0, 1
-    sig = signature(st)
-    if sig in _cache:
-        return _cache[sig]
-    if ON_MISS == "static":
-        return 0, 1
+def _scratch_desc(st, device, pre=""):
+    """Copy of the filled descriptor `st` with every pointer replaced by a scratch buffer (named pre + role: the two members of a
+    pair get buffers of their own), as the candidates are timed."""
     G = _lib.STRUCTS["FridoGemm"]
     t = G()
     C.memmove(C.addressof(t), C.addressof(st), C.sizeof(G))
@@ -151,28 +143,43 @@ def best_tile(st, device, stream):
         a_elems = st.batch * max(st.a_bs, st.a_bs2, st.M * st.lda) if (st.a_bs or st.a_bs2) else st.M * st.lda
     b_elems = st.batch * max(st.b_bs, st.b_bs2, st.N * st.ldb) if (st.b_bs or st.b_bs2) else st.N * st.ldb
     a_elems, b_elems = (a_elems + 7) // 8 * 8, (b_elems + 7) // 8 * 8
-    t.A, t.a_lo = _buf("A", a_elems * 2 * ns, device), a_elems
-    t.B, t.b_lo = _buf("B", b_elems * 2 * ns, device), b_elems
+    t.A, t.a_lo = _buf(pre + "A", a_elems * 2 * ns, device), a_elems
+    t.B, t.b_lo = _buf(pre + "B", b_elems * 2 * ns, device), b_elems
     if st.K2:
         a2 = (st.M * st.lda2 + 7) // 8 * 8
-        t.A2, t.a2_lo = _buf("A2", a2 * 2 * ns, device), a2
+        t.A2, t.a2_lo = _buf(pre + "A2", a2 * 2 * ns, device), a2
     rows = st.M * st.batch
     if st.out_f32:
-        t.out_f32 = _buf("O", max(max(st.of_bs, st.of_bs2) * st.batch, st.M * st.ldo * (4 if st.up2_phase == 5 else 1)) * 4 + 4096, device)
+        t.out_f32 = _buf(pre + "O", max(max(st.of_bs, st.of_bs2) * st.batch, st.M * st.ldo * (4 if st.up2_phase == 5 else 1)) * 4 + 4096, device)
     if st.out_op:
         n = max(max(st.oo_bs, st.oo_bs2) * st.batch, st.M * st.ldoo * (4 if st.up2_phase == 5 else 1)) + 4096
         n = (n + 7) // 8 * 8
-        t.out_op, t.oo_lo = _buf("OO", n * 2 * ns, device), n
+        t.out_op, t.oo_lo = _buf(pre + "OO", n * 2 * ns, device), n
     if st.residual:
-        t.residual = _buf("R", max(st.res_bs * st.batch, st.M * st.ldr) * 4, device)
+        t.residual = _buf(pre + "R", max(st.res_bs * st.batch, st.M * st.ldr) * 4, device)
     if st.bias:
-        t.bias = _buf("bias", st.N * 4, device)
+        t.bias = _buf(pre + "bias", st.N * 4, device)
     if st.row_bias:
-        t.row_bias = _buf("rbias", st.M * 4, device)
+        t.row_bias = _buf(pre + "rbias", st.M * 4, device)
     if st.rowvec:
-        t.rowvec, t.rowvec_step, t.rows_per_vec, t.ldv = _buf("rv", (rows + 1) * st.N * 4, device), None, max(st.rows_per_vec, 1), st.N
+        t.rowvec, t.rowvec_step, t.rows_per_vec, t.ldv = _buf(pre + "rv", (rows + 1) * st.N * 4, device), None, max(st.rows_per_vec, 1), st.N
         if st.rows_per_vec >= (1 << 29):
             t.rows_per_vec = 1 << 30
+    return t
+
+
+def best_tile(st, device, stream):
+    """st: a filled FridoGemm ctypes struct (pointers are ignored: scratch buffers are substituted).
+    Returns (tile, splitk) -- or (tile, splitk, start delay in quarter microseconds) for a signature whose pinned cache entry carries
+    one (written by tools/tune_in_context.py --stagger; this function's own timing never produces the third element)."""
+    if not ENABLED:
+        return 0, 1
+    sig = signature(st)
+    if sig in _cache:
+        return _cache[sig]
+    if ON_MISS == "static":
+        return 0, 1
+    t = _scratch_desc(st, device)
     L = _lib.lib()
     kind = _lib.OP_KINDS["FRIDO_OP_GEMM"]
     reps = 5
@@ -212,6 +219,103 @@ def best_tile(st, device, stream):
         warnings.warn(f"frido_amd.tune: no candidate tile could be timed for GEMM M={st.M} N={st.N} K={st.K}+{st.K2} batch={st.batch} "
                       f"conv={st.conv} up2_phase={st.up2_phase} ({L.frido_last_error().decode()}): it runs on the library's static tile")
     _cache[sig] = best
+    global _dirty
+    if _lib.active_planes() == "f16":
+        _dirty = True
+    return best
+
+
+PAIR_KEY = "pair"       # first element of a pair's cache key: ("pair",) + signature(a) + signature(b) -> (tile, swap); tile 0 = not paired
+PAIR_MARGIN = 0.98      # a pair must beat the two single launches by 2 %: the timing noise of ~25 us launches
+
+
+def pair_key(sa, sb):
+    return (PAIR_KEY,) + signature(sa) + signature(sb)
+
+
+def _time_graph(ops, device, inner=8, reps=5):
+    """Median device time in ms of ONE pass over `ops`: `inner` passes captured into one graph, replayed reps + 1 times on a
+    stream of the tuner's own.  None when the library rejects the program."""
+    L = _lib.lib()
+    key = ("stream", str(device))
+    if key not in _scratch:
+        _scratch[key] = torch.cuda.Stream(device=device)
+    ts = _scratch[key]
+    ts.wait_stream(torch.cuda.current_stream(device))
+    arr = _lib.pack_ops(list(ops) * inner)
+    g = C.c_void_p()
+    if L.frido_graph_capture(C.addressof(arr), len(ops) * inner, ts.cuda_stream, C.byref(g)) != 0:
+        return None
+    e0, e1 = C.c_void_p(), C.c_void_p()
+    L.frido_event_create(C.byref(e0))
+    L.frido_event_create(C.byref(e1))
+    times = []
+    try:
+        for r in range(reps + 1):
+            L.frido_event_record(e0, ts.cuda_stream)
+            if L.frido_graph_launch(g, ts.cuda_stream) != 0:
+                return None
+            L.frido_event_record(e1, ts.cuda_stream)
+            ms = C.c_float()
+            if L.frido_event_elapsed_ms(e0, e1, C.byref(ms)) != 0:
+                return None
+            times.append(ms.value / inner)
+    finally:
+        L.frido_event_destroy(e0)
+        L.frido_event_destroy(e1)
+        L.frido_graph_destroy(g)
+    return sorted(times[1:])[reps // 2]
+
+
+def pair_candidates(sa, sb):
+    """Tile ids both members of a pair take (the candidate rules of best_tile, no split-K, no conv-only tiles)."""
+    k64 = all(st.nsplit == 1 and st.K % 64 == 0 and st.K2 % 64 == 0 for st in (sa, sb))
+    big = all(st.M >= 512 and st.N >= 96 for st in (sa, sb))
+    big_tiles = (TILES8W if sa.nsplit == 1 else (7, 18, 19)) if big else ()
+    tiles = TILES + (TILES64 if k64 else ()) + big_tiles + ((17,) if big and k64 else ())
+    return [t for t in tiles if not (t % 10 in (1, 2, 4) and min(sa.M, sb.M) < 64)]
+
+
+def best_pair(sa, sb, device, measure=None, reps=5):
+    """sa, sb: the filled descriptors of two independent GEMMs emitted as a pair (engine.Prog.gemm_pair), each already carrying its
+    own best (tile, splitk).  Returns None when nothing was timed (tuner off, or a miss under FRIDO_TUNE_ON_MISS=static: the members
+    keep their tiles and the library merges them where it can), else (tile, swap): the common tile on which ONE grid of both beats the
+    members' own best launches back to back, and whether member b goes first -- or (0, 0) when the two single launches win.
+    `measure`: a dict that receives the timings (tools/gemm_pair_bench.py)."""
+    if not ENABLED:
+        return None
+    if sa.conv or sb.conv or sa.nsplit != sb.nsplit:
+        return None
+    key = pair_key(sa, sb)
+    if key in _cache:
+        return _cache[key]
+    if ON_MISS == "static":
+        return None
+    kind = _lib.OP_KINDS["FRIDO_OP_GEMM"]
+    ta, tb = _scratch_desc(sa, device, "pa:"), _scratch_desc(sb, device, "pb:")
+    for t in (ta, tb):
+        t.flags &= ~(1 << 28)
+        if t.splitk > 1:
+            t.sk_mode, t.ws = 0, workspace_for(t, device)
+    t_single = _time_graph([(kind, ta), (kind, tb)], device, reps=reps)
+    best, best_t, every = (0, 0), float("inf"), []
+    for t in (ta, tb):
+        t.splitk, t.ws = 1, None
+    for tile in pair_candidates(sa, sb):
+        ta.tile = tb.tile = tile
+        for swap in (0, 1):
+            head, tail = (tb, ta) if swap else (ta, tb)
+            head.flags |= 1 << 28
+            dt = _time_graph([(kind, head), (kind, tail)], device, reps=reps)
+            head.flags &= ~(1 << 28)
+            every.append((tile, swap, dt))
+            if dt is not None and dt < best_t:
+                best, best_t = (tile, swap), dt
+    if measure is not None:
+        measure.update(single_ms=t_single, pair_ms=best_t, tile=best[0], swap=best[1], tiles=(sa.tile, sa.splitk, sb.tile, sb.splitk), every=every)
+    if t_single is None or not best_t < PAIR_MARGIN * t_single:
+        best = (0, 0)
+    _cache[key] = best
     global _dirty
     if _lib.active_planes() == "f16":
         _dirty = True

@@ -305,8 +305,9 @@ class UNetStagePlan:
         vT = self._vt_self[(C, HW)]
         # the single-head output projection is folded into V: PV lands directly on the residual stream
         wvo, bvo = b.folded_vo_weight(t + ".attn1.to_v", t + ".attn1.to_out.0")
-        b.v_transposed(n1, C, wvo, Bx, HW, C, out=vT)
-        qp = b.linear(n1, None, wop=wq, bias=False, out="op")
+        with b.gemm_pair():      # two projections of the same rows, independent of each other
+            b.v_transposed(n1, C, wvo, Bx, HW, C, out=vT)
+            qp = b.linear(n1, None, wop=wq, bias=False, out="op")
         h2 = b.attention(qp, C, n1, C, vT, Bx, HW, HW, C, bias_ptr=bvo, residual=hcur, stream=True, ln=(t + ".norm2", 1e-5))
         qp.free()
         n1.free()
@@ -375,16 +376,19 @@ class UNetStagePlan:
                 wv, bv = wo @ wv, wo @ bv + b.h64(pre + ".proj_out.bias")
             b._wcache[key] = (pack_matrix(b.to_dev(wv), b.nsplit), b.to_dev(bv))
         wv_op, bv_dev = b._wcache[key]
-        b.v_transposed(a0, C, wv_op, Bx, HW, C, bias_ptr=None if heads == 1 else bv_dev.data_ptr(), out=vT)
+        with b.gemm_pair():      # two projections of the same rows, independent of each other
+            b.v_transposed(a0, C, wv_op, Bx, HW, C, bias_ptr=None if heads == 1 else bv_dev.data_ptr(), out=vT)
+            if heads == 1:
+                # one head, any width: q | k = the first 2 C rows of the projection, the existing single-head kernels, proj_out folded
+                # into V so that P V + bias + x lands on the residual stream
+                qk = b.linear(a0, None, wop=b.lin_weight(pre + ".qkv.weight", rows=(0, 2 * C)), bias_ptr=b.bias(pre + ".qkv.bias"), out="op")
+            else:
+                qkv = b.linear(a0, pre + ".qkv", out="op")            # [Bx*HW][3 C]: q and k stay where the projection left them
         if heads == 1:
-            # one head, any width: q | k = the first 2 C rows of the projection, the existing single-head kernels, proj_out folded
-            # into V so that P V + bias + x lands on the residual stream
-            qk = b.linear(a0, None, wop=b.lin_weight(pre + ".qkv.weight", rows=(0, 2 * C)), bias_ptr=b.bias(pre + ".qkv.bias"), out="op")
             out = b.attention(qk, 2 * C, qk, 2 * C, vT, Bx, HW, HW, C, q_off=0, k_off=C, bias_ptr=bv_dev.data_ptr(), residual=x, stream=True)
             qk.free()
             a0.free()
             return out
-        qkv = b.linear(a0, pre + ".qkv", out="op")            # [Bx*HW][3 C]: q and k stay where the projection left them
         o = b.attention_heads(qkv, 3 * C, vT, Bx, HW, heads, d, legacy=not blk.new_order)
         qkv.free()
         a0.free()

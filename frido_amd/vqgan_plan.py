@@ -62,8 +62,9 @@ def vq_attn(b, B, blk_prefix, C, x, h, w):
     vT = b._wcache[vkey]
     # proj_out folded into v (single head): PV + (W_o b_v + b_o) + x lands directly on the residual stream
     wvo, bvo = b.folded_vo_weight(pre + ".v", pre + ".proj_out")
-    b.v_transposed(a0, C, wvo, B, HW, C, out=vT)
-    qp = b.linear(a0, None, wop=wq, bias_ptr=bq, bias=False, out="op")
+    with b.gemm_pair():      # two projections of the same rows, independent of each other
+        b.v_transposed(a0, C, wvo, B, HW, C, out=vT)
+        qp = b.linear(a0, None, wop=wq, bias_ptr=bq, bias=False, out="op")
     out = b.attention(qp, C, a0, C, vT, B, HW, HW, C, bias_ptr=bvo, residual=x, stream=True)
     qp.free()
     a0.free()

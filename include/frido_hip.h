@@ -146,7 +146,10 @@ typedef struct FridoGemm {
                                    one-workgroup-per-CU kernels too (odd XCDs of the first 256 workgroups wait);
                                    bit 27 (r06): the ring kernel walks its output tiles in COLUMN PANELS (P = 8 columns x all rows, P halved while the weight panel
                                    exceeds 3 MB) instead of row-major, so that an XCD's concurrent workgroups share an L2-resident weight panel;
-                                   a pure re-ordering of independent tiles, results unchanged */
+                                   a pure re-ordering of independent tiles, results unchanged;
+                                   bit 28: PAIRED with the next op of the program -- frido_run / frido_graph_capture / frido_run_timed hand this GEMM
+                                   and the next op, which must be a FRIDO_OP_GEMM on the same stream, to frido_gemm_pair (below): two independent
+                                   GEMMs in one grid where their tiles allow it, results unchanged.  frido_gemm itself ignores the bit */
     /* optional uint8 image output (r04: the output path of scripts/sample_diffusion.py fused into the decoder's last conv --
        the all-gather and the NPZ / PNG writers then move uint8): out_u8[row * ldu8 + n] for n < N, NHWC.  u8_mode 1 =
        custom_to_np (sample_diffusion.py:115-121): ((x + 1) * 127.5) clamped to [0, 255], truncated; 2 = custom_to_pil
@@ -617,6 +620,13 @@ int frido_gemm(const FridoGemm* d, frido_stream_t s);
  * (one per stream is enough: launches on a stream are ordered); a host that is not the bundled Python runtime sizes it with
  * this call instead of reading frido_amd/tune.py. */
 int64_t frido_gemm_workspace_bytes(const FridoGemm* d);
+/* Two INDEPENDENT GEMMs (neither reads what the other writes) as a drop-in for frido_gemm(a) followed by frido_gemm(b): both
+ * descriptors are checked as frido_gemm checks them BEFORE anything is launched, and every output is bit for bit what the two calls
+ * write.  ONE grid runs both -- member a's workgroups first, then member b's, each running its unchanged tile program, so that one
+ * member's prologue and store drain overlap the other's k-loop -- when both are dense (conv == 0), both have splitk <= 1, their nsplit
+ * is the same and their tiles (tile == 0: the static choice, as in frido_gemm) resolve to the same kernel of tiles 1..8 / 11..19.
+ * Otherwise the two launches follow each other.  In a pair launch the start-stagger bits of `flags` (8..26) are ignored. */
+int frido_gemm_pair(const FridoGemm* a, const FridoGemm* b, frido_stream_t s);
 int frido_gn_stats(const FridoGnStats* d, frido_stream_t s);
 int frido_gn_apply(const FridoGnApply* d, frido_stream_t s);
 int frido_layernorm(const FridoLayerNorm* d, frido_stream_t s);

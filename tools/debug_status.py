@@ -17,7 +17,7 @@ def walk(prog, name, sp):
     names = {v: k[len("FRIDO_OP_"):] for k, v in _lib.OP_KINDS.items()}
     bad = 0
     for i, (kind, st) in enumerate(prog.ops):
-        arr = _lib.pack_ops([(kind, st)])
+        arr = _lib.pack_single(kind, st)
         _lib.check(_lib.lib().frido_run(C.addressof(arr), 1, sp), "run")
         f = _lib.status_flags(clear=True)
         if f:

@@ -17,7 +17,7 @@ def dev_copy(ptr, nbytes, sp):
     n = (nbytes + 15) // 16 * 16
     t = torch.empty(n, dtype=torch.uint8, device="cuda")
     kind, st = _lib.make_op("FRIDO_OP_COPY", src=ptr, dst=t.data_ptr(), n=n)
-    arr = _lib.pack_ops([(kind, st)])
+    arr = _lib.pack_single(kind, st)
     _lib.check(_lib.lib().frido_run(C.addressof(arr), 1, sp), "copy")
     torch.cuda.synchronize()
     return t[:nbytes]
@@ -39,7 +39,7 @@ def check_prog(prog, name, sp, step_val, quiet=False):
         if names[kind] == "GN_FUSED" and st.sk_ws and st.sk_residual:      # the residual may be updated IN PLACE (sk_out == sk_residual): read it first
             torch.cuda.synchronize()
             res_before = f32(st.sk_residual, (st.B * st.HW, st.sk_ldr), sp)
-        arr = _lib.pack_ops([(kind, st)])
+        arr = _lib.pack_single(kind, st)
         _lib.check(_lib.lib().frido_run(C.addressof(arr), 1, sp), "run")
         if names[kind] != "GN_FUSED" or not st.sk_ws:
             continue
