@@ -1,8 +1,6 @@
 // Shared device helpers for libfrido_hip (gfx950 only).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "frido_hip.h"
+#include "launch.h"      // the launcher toolkit: FRIDO_REQUIRE, grid_for, aligned16, load_vec / store_vec, nonfinite, guided_eps
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -10,17 +8,6 @@ typedef __attribute__((ext_vector_type(8))) float f32x8;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 #define FRIDO_WAVE 64
-
-void frido_set_error(const char* fmt, ...);
-int frido_check_launch(const char* what);
-
-#define FRIDO_REQUIRE(cond, msg)                                            \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            frido_set_error("%s: %s (%s)", __func__, msg, #cond);           \
-            return FRIDO_EINVAL;                                            \
-        }                                                                   \
-    } while (0)
 
 // round-to-nearest-even fp32 -> bf16 bits (inputs are finite on this path)
 __device__ __forceinline__ uint32_t f32_to_bf16_bits(float f) {

@@ -4,38 +4,10 @@
 // active element it reads x, eps (twice under guidance) and -- on a second-order row -- the previous x0, and writes x', x0 and the history.
 #include "common.h"
 
-#define DPM_REQUIRE(cond, msg)                                              \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            frido_set_error("%s: %s (%s)", __func__, msg, #cond);           \
-            return FRIDO_EINVAL;                                            \
-        }                                                                   \
-    } while (0)
-
 namespace {
 
 constexpr int DPM_ROW = 8;      // inv_alpha, sigma, c_x, c_d, w_cur, w_last, pad x2 (frido_amd/schedules.py dpm_solver_rows)
-
-inline int grid_for(int64_t work_items, int cap = 2048) {
-    int64_t b = (work_items + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-template <int V>
-__device__ __forceinline__ void load_vec(const float* p, float v[V]) {
-    if constexpr (V == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-        v[0] = *p;
-    }
-}
-template <int V>
-__device__ __forceinline__ void store_vec(float* p, const float v[V]) {
-    if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else *p = v[0];
-}
+constexpr int DPM_GRID_CAP = 2048;
 
 // One unit = V consecutive channels of one pixel among channels [0, start + nch).  V == 4: Cx, start and nch are multiples of 4, so a unit
 // is frozen or active as a whole and one 16-byte access on every tensor.  V == 1: any channel counts.  Channels from start + nch on are
@@ -69,11 +41,11 @@ __global__ __launch_bounds__(256) void dpm_step_kernel(const FridoDpmStep d, int
 #pragma unroll
         for (int k = 0; k < V; ++k) {
             float ev = e[k];
-            if (d.eps_uncond) ev = __fadd_rn(eu[k], __fmul_rn(cfg, __fsub_rn(ev, eu[k])));
+            if (d.eps_uncond) ev = guided_eps(ev, eu[k], cfg);
             x0[k] = __fmul_rn(__fsub_rn(xv[k], __fmul_rn(sigma, ev)), inv_alpha);
             const float D = second ? __fadd_rn(__fmul_rn(w_cur, x0[k]), __fmul_rn(w_last, h[k])) : x0[k];
             xo[k] = __fadd_rn(__fmul_rn(c_x, xv[k]), __fmul_rn(c_d, D));
-            bad |= !(fabsf(xo[k]) <= 3.0e38f);
+            bad |= nonfinite(xo[k]);
         }
         store_vec<V>(d.x_out + xi, xo);
         if (d.pred_x0) store_vec<V>(d.pred_x0 + xi, x0);
@@ -85,17 +57,17 @@ __global__ __launch_bounds__(256) void dpm_step_kernel(const FridoDpmStep d, int
 }  // namespace
 
 extern "C" int frido_dpm_step(const FridoDpmStep* d, frido_stream_t s) {
-    DPM_REQUIRE(d && d->x && d->eps_cond && d->coef && d->x_out && d->x0_hist, "null pointer");
-    DPM_REQUIRE(d->B > 0 && d->HW > 0 && d->Cx > 0 && d->nch > 0, "B, HW, Cx and nch must be positive");
-    DPM_REQUIRE(d->start >= 0 && (int64_t)d->start + d->nch <= d->Cx, "the channel range must lie inside [0, Cx]");
-    DPM_REQUIRE(d->cfg_scale == d->cfg_scale, "cfg_scale is NaN");
+    FRIDO_REQUIRE(d && d->x && d->eps_cond && d->coef && d->x_out && d->x0_hist, "null pointer");
+    FRIDO_REQUIRE(d->B > 0 && d->HW > 0 && d->Cx > 0 && d->nch > 0, "B, HW, Cx and nch must be positive");
+    FRIDO_REQUIRE(d->start >= 0 && (int64_t)d->start + d->nch <= d->Cx, "the channel range must lie inside [0, Cx]");
+    FRIDO_REQUIRE(d->cfg_scale == d->cfg_scale, "cfg_scale is NaN");
     const int end = d->start + d->nch;
     const bool vec = d->Cx % 4 == 0 && d->start % 4 == 0 && d->nch % 4 == 0 && aligned16(d->x) && aligned16(d->x_out) && aligned16(d->pred_x0) &&
                      aligned16(d->eps_cond) && aligned16(d->eps_uncond) && aligned16(d->x0_hist);
     const int64_t n = (int64_t)d->B * d->HW * end;
     if (vec)
-        hipLaunchKernelGGL(dpm_step_kernel<4>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)s, *d, n / 4);
+        hipLaunchKernelGGL(dpm_step_kernel<4>, dim3(grid_for(n / 4, DPM_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d, n / 4);
     else
-        hipLaunchKernelGGL(dpm_step_kernel<1>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, *d, n);
+        hipLaunchKernelGGL(dpm_step_kernel<1>, dim3(grid_for(n, DPM_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d, n);
     return frido_check_launch("dpm_step");
 }

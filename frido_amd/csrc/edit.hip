@@ -10,22 +10,11 @@
 // is never 16-byte aligned, so a vector path would serve no shipped shape.
 #include "common.h"
 
-#define EDIT_REQUIRE(cond, msg)                                             \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            frido_set_error("%s: %s (%s)", __func__, msg, #cond);           \
-            return FRIDO_EINVAL;                                            \
-        }                                                                   \
-    } while (0)
-
 namespace {
 
 #include "philox.h"      // the generator of frido_randn and the sampler updates (misc.hip includes the same file)
 
-inline int grid_for(int64_t work_items, int cap = 2048) {
-    int64_t b = (work_items + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
+constexpr int EDIT_GRID_CAP = 2048;
 
 // Unit i = (pixel i / ngrp of the batch, group i % ngrp of its window): window channels [4 g, min(4 g + 4, c1 - c0)).
 __global__ __launch_bounds__(256) void keep_blend_kernel(const FridoKeepBlend d, int ngrp, int64_t units) {
@@ -56,7 +45,7 @@ __global__ __launch_bounds__(256) void keep_blend_kernel(const FridoKeepBlend d,
             const float z = d.z0[xi + k];
             const float q = d.clean ? z : __fadd_rn(__fmul_rn(sa, z), __fmul_rn(sb, n[k]));
             const float o = d.mask ? __fadd_rn(__fmul_rn(q, m), __fmul_rn(__fsub_rn(1.0f, m), d.x[xi + k])) : q;
-            bad |= !(fabsf(o) <= 3.0e38f);
+            bad |= nonfinite(o);
             d.x[xi + k] = o;
         }
     }
@@ -66,18 +55,18 @@ __global__ __launch_bounds__(256) void keep_blend_kernel(const FridoKeepBlend d,
 }  // namespace
 
 extern "C" int frido_keep_blend(const FridoKeepBlend* d, frido_stream_t s) {
-    EDIT_REQUIRE(d && d->x && d->z0, "null pointer");
-    EDIT_REQUIRE(d->clean == 0 || d->clean == 1, "clean is 0 or 1");
-    EDIT_REQUIRE(d->clean || d->qtab, "null pointer: the coefficient table (only clean = 1 does without)");
-    EDIT_REQUIRE(d->B > 0 && d->HW > 0 && d->Cx > 0, "B, HW and Cx must be positive");
-    EDIT_REQUIRE(d->c0 >= 0 && d->c0 < d->c1 && d->c1 <= d->Cx, "the channel window must be non-empty and lie inside [0, Cx]");
-    EDIT_REQUIRE(d->row_offset >= 0, "row_offset must not be negative");
-    EDIT_REQUIRE(!(d->noise && (d->rng_dev || d->seed || d->sample0 || d->rng_stream)), "a noise tape together with a Philox key: one noise form per launch");
-    EDIT_REQUIRE(!d->noise || (d->noise_C >= d->c1 && d->noise_stride >= 0), "the noise tape holds the channels reached so far: noise_C >= c1, noise_stride >= 0");
-    EDIT_REQUIRE(!(d->clean && (d->noise || d->rng_dev)), "clean = 1 reads no noise: pass neither a tape nor rng_dev");
+    FRIDO_REQUIRE(d && d->x && d->z0, "null pointer");
+    FRIDO_REQUIRE(d->clean == 0 || d->clean == 1, "clean is 0 or 1");
+    FRIDO_REQUIRE(d->clean || d->qtab, "null pointer: the coefficient table (only clean = 1 does without)");
+    FRIDO_REQUIRE(d->B > 0 && d->HW > 0 && d->Cx > 0, "B, HW and Cx must be positive");
+    FRIDO_REQUIRE(d->c0 >= 0 && d->c0 < d->c1 && d->c1 <= d->Cx, "the channel window must be non-empty and lie inside [0, Cx]");
+    FRIDO_REQUIRE(d->row_offset >= 0, "row_offset must not be negative");
+    FRIDO_REQUIRE(!(d->noise && (d->rng_dev || d->seed || d->sample0 || d->rng_stream)), "a noise tape together with a Philox key: one noise form per launch");
+    FRIDO_REQUIRE(!d->noise || (d->noise_C >= d->c1 && d->noise_stride >= 0), "the noise tape holds the channels reached so far: noise_C >= c1, noise_stride >= 0");
+    FRIDO_REQUIRE(!(d->clean && (d->noise || d->rng_dev)), "clean = 1 reads no noise: pass neither a tape nor rng_dev");
     const int ngrp = (d->c1 - d->c0 + 3) >> 2;
-    EDIT_REQUIRE((int64_t)d->HW * ngrp < ((int64_t)1 << 32), "a sample has more Philox groups than the 32-bit group counter holds");
+    FRIDO_REQUIRE((int64_t)d->HW * ngrp < ((int64_t)1 << 32), "a sample has more Philox groups than the 32-bit group counter holds");
     const int64_t units = (int64_t)d->B * d->HW * ngrp;
-    hipLaunchKernelGGL(keep_blend_kernel, dim3(grid_for(units)), dim3(256), 0, (hipStream_t)s, *d, ngrp, units);
+    hipLaunchKernelGGL(keep_blend_kernel, dim3(grid_for(units, EDIT_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d, ngrp, units);
     return frido_check_launch("keep_blend");
 }

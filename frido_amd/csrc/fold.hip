@@ -1,30 +1,13 @@
 // Patch-wise ("convolutional") mode of FridoDiffusion (frido/models/diffusion/frido.py:714-764, 1076-1152): the crops of an NHWC
 // f32 map (nn.Unfold) and their weighted, normalised recombination (nn.Fold of o * weighting, divided by fold(weighting)).
-// Plain f32 arithmetic: no operand planes, so no status word (common.h is not included on purpose -- it would register one) and
+// Plain f32 arithmetic: no operand planes, so no status word (launch.h alone: common.h is not included on purpose -- it would register one) and
 // the two builds of the library compile the same code.  Both kernels move every byte once and are bandwidth-bound.
 // Batch layout of the crop tensor (include/frido_hip.h): crop l of sample b is entry b * L + l.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "frido_hip.h"
-
-void frido_set_error(const char* fmt, ...);
-int frido_check_launch(const char* what);
-
-#define FOLD_REQUIRE(cond, msg)                                             \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            frido_set_error("%s: %s (%s)", __func__, msg, #cond);           \
-            return FRIDO_EINVAL;                                            \
-        }                                                                   \
-    } while (0)
+#include "launch.h"
 
 namespace {
 
-inline int grid_for(int64_t work_items, int cap = 8192) {
-    int64_t b = (work_items + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
+constexpr int FOLD_GRID_CAP = 8192;
 
 // One unit = V consecutive floats of a crop row (kw * C contiguous floats in the source AND in the destination).
 template <int V>
@@ -107,34 +90,33 @@ __global__ __launch_bounds__(256) void fold_kernel(const FridoFold d, int Ly, in
 inline bool geometry_ok(int H, int W, int kh, int kw, int sy, int sx) {
     return H > 0 && W > 0 && kh > 0 && kw > 0 && sy > 0 && sx > 0 && kh <= H && kw <= W && (H - kh) % sy == 0 && (W - kw) % sx == 0;
 }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
 extern "C" int frido_unfold(const FridoUnfold* d, frido_stream_t s) {
-    FOLD_REQUIRE(d && d->src && d->dst && d->B > 0 && d->C > 0, "bad arguments");
-    FOLD_REQUIRE(geometry_ok(d->H, d->W, d->kh, d->kw, d->sy, d->sx), "the crops must tile the map exactly: (H - kh) % sy == 0 and (W - kw) % sx == 0");
+    FRIDO_REQUIRE(d && d->src && d->dst && d->B > 0 && d->C > 0, "bad arguments");
+    FRIDO_REQUIRE(geometry_ok(d->H, d->W, d->kh, d->kw, d->sy, d->sx), "the crops must tile the map exactly: (H - kh) % sy == 0 and (W - kw) % sx == 0");
     const int Ly = (d->H - d->kh) / d->sy + 1, Lx = (d->W - d->kw) / d->sx + 1, L = Ly * Lx;
     const int64_t floats = (int64_t)d->B * L * d->kh * d->kw * d->C;
     // 16-byte accesses where every crop row starts on a 16-byte boundary on both sides and is a whole number of vectors long
     const bool vec = (d->kw * d->C) % 4 == 0 && (d->W * d->C) % 4 == 0 && (d->sx * d->C) % 4 == 0 && aligned16(d->src) && aligned16(d->dst);
     if (vec)
-        hipLaunchKernelGGL(unfold_kernel<4>, dim3(grid_for(floats / 4)), dim3(256), 0, (hipStream_t)s, *d, Lx, L, floats / 4);
+        hipLaunchKernelGGL(unfold_kernel<4>, dim3(grid_for(floats / 4, FOLD_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d, Lx, L, floats / 4);
     else
-        hipLaunchKernelGGL(unfold_kernel<1>, dim3(grid_for(floats)), dim3(256), 0, (hipStream_t)s, *d, Lx, L, floats);
+        hipLaunchKernelGGL(unfold_kernel<1>, dim3(grid_for(floats, FOLD_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d, Lx, L, floats);
     return frido_check_launch("unfold");
 }
 
 extern "C" int frido_fold(const FridoFold* d, frido_stream_t s) {
-    FOLD_REQUIRE(d && d->crops && d->wt && d->norm && (d->out || d->out_u8) && d->B > 0 && d->C > 0, "bad arguments");
-    FOLD_REQUIRE(geometry_ok(d->H, d->W, d->kh, d->kw, d->sy, d->sx), "the crops must tile the map exactly: (H - kh) % sy == 0 and (W - kw) % sx == 0");
-    FOLD_REQUIRE(!d->out_u8 || d->u8_mode == 1 || d->u8_mode == 2, "out_u8: u8_mode 1 (custom_to_np) or 2 (custom_to_pil)");
+    FRIDO_REQUIRE(d && d->crops && d->wt && d->norm && (d->out || d->out_u8) && d->B > 0 && d->C > 0, "bad arguments");
+    FRIDO_REQUIRE(geometry_ok(d->H, d->W, d->kh, d->kw, d->sy, d->sx), "the crops must tile the map exactly: (H - kh) % sy == 0 and (W - kw) % sx == 0");
+    FRIDO_REQUIRE(!d->out_u8 || d->u8_mode == 1 || d->u8_mode == 2, "out_u8: u8_mode 1 (custom_to_np) or 2 (custom_to_pil)");
     const int Ly = (d->H - d->kh) / d->sy + 1, Lx = (d->W - d->kw) / d->sx + 1;
     const int64_t floats = (int64_t)d->B * d->H * d->W * d->C;
     const bool vec = d->C % 4 == 0 && aligned16(d->crops) && (!d->out || aligned16(d->out));
     if (vec)
-        hipLaunchKernelGGL(fold_kernel<4>, dim3(grid_for(floats / 4)), dim3(256), 0, (hipStream_t)s, *d, Ly, Lx, floats / 4);
+        hipLaunchKernelGGL(fold_kernel<4>, dim3(grid_for(floats / 4, FOLD_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d, Ly, Lx, floats / 4);
     else
-        hipLaunchKernelGGL(fold_kernel<1>, dim3(grid_for(floats)), dim3(256), 0, (hipStream_t)s, *d, Ly, Lx, floats);
+        hipLaunchKernelGGL(fold_kernel<1>, dim3(grid_for(floats, FOLD_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d, Ly, Lx, floats);
     return frido_check_launch("fold");
 }

@@ -2,7 +2,7 @@
 // with the guidance rescale of Lin et al. 2024, not in the reference: FridoGuidanceCompose in include/frido_hip.h.  eps holds n + 1 slots
 // of B * per_sample floats -- the conditionings' eps first, the unconditional one last -- and w[0 .. n) the weights, w[n] = phi, on the device:
 //   acc = e_u;   for i = 0 .. n - 1, in this order:   acc = acc + w_i * (e_i - e_u)
-//        -- per term sampler_step_kernel's expression (misc.hip): __fadd_rn(acc, __fmul_rn(w_i, __fsub_rn(e_i, e_u))); n = 1 is its mix, bit for bit
+//        -- per term guided_eps's operations (launch.h): __fadd_rn(acc, __fmul_rn(w_i, __fsub_rn(e_i, e_u))); n = 1 is its mix, bit for bit
 //   plain form:     out = acc
 //   rescaled form:  out = acc * f_b,   f_b = phi * sigma(e_0) / sigma(acc) + (1 - phi)   per sample b over its per_sample elements
 // in plain f32, every product and sum rounded on its own (no FMA contraction), so the two builds of the library compile the same kernels;
@@ -15,39 +15,10 @@
 // captured step body, in front of whichever update kernel follows.
 #include "common.h"
 
-#define GUIDE_REQUIRE(cond, msg)                                            \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            frido_set_error("%s: %s (%s)", __func__, msg, #cond);           \
-            return FRIDO_EINVAL;                                            \
-        }                                                                   \
-    } while (0)
-
 namespace {
 
 constexpr int GUIDE_MAX = 8;            // conditionings per launch
 constexpr int GUIDE_GRID_CAP = 2048;
-
-inline int grid_for(int64_t work_items, int cap = GUIDE_GRID_CAP) {
-    int64_t b = (work_items + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-template <int V>
-__device__ __forceinline__ void load_vec(const float* p, float v[V]) {
-    if constexpr (V == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-        v[0] = *p;
-    }
-}
-template <int V>
-__device__ __forceinline__ void store_vec(float* p, const float v[V]) {
-    if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else *p = v[0];
-}
 
 // The weights in registers: statically indexed (the loops over them are fully unrolled under `i < n`), so nothing spills.
 struct Weights { float w[GUIDE_MAX]; };
@@ -90,7 +61,7 @@ __global__ __launch_bounds__(256) void guidance_compose_kernel(const FridoGuidan
         float acc[V], e0[V];
         compose<V>(d.eps, stride, i * V, d.n, wt, acc, e0);
 #pragma unroll
-        for (int k = 0; k < V; ++k) bad |= !(fabsf(acc[k]) <= 3.0e38f);
+        for (int k = 0; k < V; ++k) bad |= nonfinite(acc[k]);
         store_vec<V>(d.out + i * V, acc);
     }
     status_raise(false, bad);
@@ -137,7 +108,7 @@ __global__ __launch_bounds__(256) void guidance_rescale_kernel(const FridoGuidan
     bool bad = false;
     for (int64_t j = threadIdx.x; j < d.per_sample; j += 256) {
         const float o = __fmul_rn(d.out[base + j], f);
-        bad |= !(fabsf(o) <= 3.0e38f);
+        bad |= nonfinite(o);
         d.out[base + j] = o;
     }
     status_raise(false, bad);
@@ -146,20 +117,20 @@ __global__ __launch_bounds__(256) void guidance_rescale_kernel(const FridoGuidan
 }  // namespace
 
 extern "C" int frido_guidance_compose(const FridoGuidanceCompose* d, frido_stream_t s) {
-    GUIDE_REQUIRE(d && d->eps && d->out && d->weights, "null pointer");
-    GUIDE_REQUIRE(d->n >= 1 && d->n <= GUIDE_MAX, "1 to 8 conditionings");
-    GUIDE_REQUIRE(d->B > 0 && d->per_sample > 0, "B and per_sample must be positive");
+    FRIDO_REQUIRE(d && d->eps && d->out && d->weights, "null pointer");
+    FRIDO_REQUIRE(d->n >= 1 && d->n <= GUIDE_MAX, "1 to 8 conditionings");
+    FRIDO_REQUIRE(d->B > 0 && d->per_sample > 0, "B and per_sample must be positive");
     const int64_t total = (int64_t)d->B * d->per_sample;
     // out may BE slot 0; any other overlap with the slots would let one thread's result reach another thread's input
     const float* lo = d->eps + (d->out == d->eps ? total : 0);
     const float* hi = d->eps + (int64_t)(d->n + 1) * total;
-    GUIDE_REQUIRE(d->out + total <= lo || d->out >= hi, "out may alias slot 0 exactly and must not overlap any other slot");
+    FRIDO_REQUIRE(d->out + total <= lo || d->out >= hi, "out may alias slot 0 exactly and must not overlap any other slot");
     if (d->rescale) {
         hipLaunchKernelGGL(guidance_rescale_kernel, dim3(d->B), dim3(256), 0, (hipStream_t)s, *d);
     } else if (total % 4 == 0 && aligned16(d->eps) && aligned16(d->out)) {
-        hipLaunchKernelGGL(guidance_compose_kernel<4>, dim3(grid_for(total / 4)), dim3(256), 0, (hipStream_t)s, *d, total / 4);
+        hipLaunchKernelGGL(guidance_compose_kernel<4>, dim3(grid_for(total / 4, GUIDE_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d, total / 4);
     } else {
-        hipLaunchKernelGGL(guidance_compose_kernel<1>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, *d, total);
+        hipLaunchKernelGGL(guidance_compose_kernel<1>, dim3(grid_for(total, GUIDE_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d, total);
     }
     return frido_check_launch("guidance_compose");
 }

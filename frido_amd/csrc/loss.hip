@@ -1,32 +1,14 @@
 // The diffusion objective of FridoDiffusion (frido/models/diffusion/frido.py): q_sample as p_losses calls it (:302-318, 1184) and the
-// loss of one stage (:1196-1222).  Plain f32 / f64 arithmetic: no operand planes, so no status word (common.h is not included on purpose
+// loss of one stage (:1196-1222).  Plain f32 / f64 arithmetic: no operand planes, so no status word (launch.h alone: common.h is not included on purpose
 // -- it would register one) and the two builds of the library compile the same code.  Both kernels are bandwidth-bound.
 // Noise is a tape [B][HW][Cx] or Philox4x32-10 in frido_randn's numbering (misc.hip: 4-float groups over the flat sample [HW][Cx],
 // draw 0, key (seed, sample0 + b, rng_stream)); the loss kernel regenerates its target from the same key, so no noise tensor exists
 // in Philox mode.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "frido_hip.h"
-
-void frido_set_error(const char* fmt, ...);
-int frido_check_launch(const char* what);
-
-#define LOSS_REQUIRE(cond, msg)                                             \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            frido_set_error("%s: %s (%s)", __func__, msg, #cond);           \
-            return FRIDO_EINVAL;                                            \
-        }                                                                   \
-    } while (0)
+#include "launch.h"
 
 namespace {
 
-inline int grid_for(int64_t work_items, int cap = 8192) {
-    int64_t b = (work_items + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+constexpr int LOSS_GRID_CAP = 8192;
 
 #include "philox.h"      // the generator of frido_randn (misc.hip includes the same file)
 
@@ -36,16 +18,6 @@ __device__ __forceinline__ int table_row(const int64_t* t, int64_t b, int T) {  
 }
 
 // ---- q_sample ----------------------------------------------------------------------------------------------------------------------
-// V consecutive values of a [..][Cx]-strided tensor: one 16-byte access (V == 4) or one scalar.
-template <int V>
-__device__ __forceinline__ void load_vec(const float* p, float v[V]) {
-    if constexpr (V == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-        v[0] = *p;
-    }
-}
 // The noise of elements [e, e + V) of sample `sample`'s flat [HW][Cx]: from the tape, else the Philox group that holds them (V == 4: e is a
 // multiple of 4, the unit is exactly one group; V == 1: the group is drawn whole and one lane of it used).
 template <int V>
@@ -159,34 +131,34 @@ __global__ __launch_bounds__(64) void loss_row_kernel(const FridoDiffusionLoss d
 }  // namespace
 
 extern "C" int frido_qsample(const FridoQSample* d, frido_stream_t s) {
-    LOSS_REQUIRE(d && d->x0 && d->x_noisy && d->t && d->sqrt_ac && d->sqrt_1mac, "null pointer");
-    LOSS_REQUIRE(d->B > 0 && d->HW > 0 && d->Cx > 0 && d->T > 0, "B, HW, Cx and T must be positive");
-    LOSS_REQUIRE(d->ch_start >= 0 && d->ch_start < d->ch_end && d->ch_end <= d->Cx, "the channel range must lie inside [0, Cx]");
-    LOSS_REQUIRE(d->mix_tau == d->mix_tau, "mix_tau is NaN");
-    LOSS_REQUIRE(d->noise || ((int64_t)d->HW * d->Cx) % 4 == 0, "Philox noise is numbered in groups of 4 floats: HW * Cx must be a multiple of 4");
-    LOSS_REQUIRE((int64_t)d->HW * d->Cx < ((int64_t)1 << 33), "a sample has more Philox groups than the 32-bit group counter holds");
+    FRIDO_REQUIRE(d && d->x0 && d->x_noisy && d->t && d->sqrt_ac && d->sqrt_1mac, "null pointer");
+    FRIDO_REQUIRE(d->B > 0 && d->HW > 0 && d->Cx > 0 && d->T > 0, "B, HW, Cx and T must be positive");
+    FRIDO_REQUIRE(d->ch_start >= 0 && d->ch_start < d->ch_end && d->ch_end <= d->Cx, "the channel range must lie inside [0, Cx]");
+    FRIDO_REQUIRE(d->mix_tau == d->mix_tau, "mix_tau is NaN");
+    FRIDO_REQUIRE(d->noise || ((int64_t)d->HW * d->Cx) % 4 == 0, "Philox noise is numbered in groups of 4 floats: HW * Cx must be a multiple of 4");
+    FRIDO_REQUIRE((int64_t)d->HW * d->Cx < ((int64_t)1 << 33), "a sample has more Philox groups than the 32-bit group counter holds");
     const bool vec = d->Cx % 4 == 0 && d->ch_end % 4 == 0;
-    LOSS_REQUIRE(!vec || (aligned16(d->x0) && aligned16(d->x_noisy) && aligned16(d->noise)), "16-byte accesses: x0, x_noisy and noise must be 16-byte aligned");
+    FRIDO_REQUIRE(!vec || (aligned16(d->x0) && aligned16(d->x_noisy) && aligned16(d->noise)), "16-byte accesses: x0, x_noisy and noise must be 16-byte aligned");
     // torch multiplies the f32 tensor by the Python doubles (1 - mix_tau) and mix_tau, each cast to f32
     const float keep = (float)(1.0 - d->mix_tau), mix = (float)d->mix_tau;
     const int64_t n = (int64_t)d->B * d->HW * d->ch_end;
     if (vec)
-        hipLaunchKernelGGL(qsample_kernel<4>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)s, *d, keep, mix, n / 4);
+        hipLaunchKernelGGL(qsample_kernel<4>, dim3(grid_for(n / 4, LOSS_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d, keep, mix, n / 4);
     else
-        hipLaunchKernelGGL(qsample_kernel<1>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, *d, keep, mix, n);
+        hipLaunchKernelGGL(qsample_kernel<1>, dim3(grid_for(n, LOSS_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d, keep, mix, n);
     return frido_check_launch("qsample");
 }
 
 extern "C" int frido_diffusion_loss(const FridoDiffusionLoss* d, frido_stream_t s) {
-    LOSS_REQUIRE(d && d->pred && d->per_sample, "null pointer");
-    LOSS_REQUIRE(!d->out || (d->t && d->logvar && d->lvlb_weights && d->T > 0), "the stage row needs t, logvar, lvlb_weights and T");
-    LOSS_REQUIRE(d->B > 0 && d->HW > 0 && d->Cx > 0 && d->nch > 0, "B, HW, Cx and nch must be positive");
-    LOSS_REQUIRE(d->ch_start >= 0 && (int64_t)d->ch_start + d->nch <= d->Cx, "the channel range must lie inside [0, Cx]");
-    LOSS_REQUIRE(d->loss_type == 0 || d->loss_type == 1, "unknown loss type: 0 (l1) or 1 (l2)");
-    LOSS_REQUIRE(d->noise || ((int64_t)d->HW * d->Cx) % 4 == 0, "Philox noise is numbered in groups of 4 floats: HW * Cx must be a multiple of 4");
-    LOSS_REQUIRE((int64_t)d->HW * d->Cx < ((int64_t)1 << 33), "a sample has more Philox groups than the 32-bit group counter holds");
+    FRIDO_REQUIRE(d && d->pred && d->per_sample, "null pointer");
+    FRIDO_REQUIRE(!d->out || (d->t && d->logvar && d->lvlb_weights && d->T > 0), "the stage row needs t, logvar, lvlb_weights and T");
+    FRIDO_REQUIRE(d->B > 0 && d->HW > 0 && d->Cx > 0 && d->nch > 0, "B, HW, Cx and nch must be positive");
+    FRIDO_REQUIRE(d->ch_start >= 0 && (int64_t)d->ch_start + d->nch <= d->Cx, "the channel range must lie inside [0, Cx]");
+    FRIDO_REQUIRE(d->loss_type == 0 || d->loss_type == 1, "unknown loss type: 0 (l1) or 1 (l2)");
+    FRIDO_REQUIRE(d->noise || ((int64_t)d->HW * d->Cx) % 4 == 0, "Philox noise is numbered in groups of 4 floats: HW * Cx must be a multiple of 4");
+    FRIDO_REQUIRE((int64_t)d->HW * d->Cx < ((int64_t)1 << 33), "a sample has more Philox groups than the 32-bit group counter holds");
     const bool vec = d->Cx % 4 == 0 && d->ch_start % 4 == 0 && d->nch % 4 == 0;
-    LOSS_REQUIRE(!vec || (aligned16(d->pred) && aligned16(d->noise)), "16-byte accesses: pred and noise must be 16-byte aligned");
+    FRIDO_REQUIRE(!vec || (aligned16(d->pred) && aligned16(d->noise)), "16-byte accesses: pred and noise must be 16-byte aligned");
     if (vec)
         hipLaunchKernelGGL(loss_sample_kernel<4>, dim3(d->B), dim3(256), 0, (hipStream_t)s, *d);
     else

@@ -6,10 +6,7 @@
 
 namespace {
 
-inline int grid_for(int64_t work_items, int cap = 8192) {
-    int64_t b = (work_items + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
+constexpr int MISC_GRID_CAP = 8192, STEP_GRID_CAP = 2048;      // grid_for caps: the streaming kernels; the two state updates
 
 // ---- f32 -> operand with channel slice + zero pad --------------------------------------------
 __global__ __launch_bounds__(256) void pack_kernel(const FridoPack d) {
@@ -203,7 +200,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const FridoSamplerSte
             float e = d.eps_cond[ei];
             if (d.eps_uncond) {
                 const float eu = d.eps_uncond[ei];
-                e = __fadd_rn(eu, __fmul_rn(cfg, __fsub_rn(e, eu)));
+                e = guided_eps(e, eu, cfg);
             }
             if (eout) eout[ei] = e;
             if (h1) {
@@ -280,7 +277,7 @@ __global__ __launch_bounds__(256) void ancestral_step_kernel(const FridoSamplerS
             const float nv = c < d.start ? 0.f : nz[e];
             x0v[e] = x0;
             xo[e] = __fadd_rn(mean, __fmul_rn(sigma, __fmul_rn(nv, d.temperature)));
-            bad |= !(fabsf(xo[e]) <= 3.0e38f);
+            bad |= nonfinite(xo[e]);
             if (++c == d.Cx) { c = 0; ++pix; }
         }
         if (d.pred_x0) reinterpret_cast<float4*>(d.pred_x0)[g] = make_float4(x0v[0], x0v[1], x0v[2], x0v[3]);
@@ -412,14 +409,14 @@ __global__ __launch_bounds__(256) void fill_kernel(const FridoFill d) {
 extern "C" int frido_pack(const FridoPack* d, frido_stream_t s) {
     FRIDO_REQUIRE(d && d->src && d->out_op, "null pointer");
     FRIDO_REQUIRE((d->Cpad & 3) == 0 && d->Cuse <= d->Cpad && d->c0 + d->Cuse <= d->Csrc && d->Cuse > 0, "bad channel slice");
-    hipLaunchKernelGGL(pack_kernel, dim3(grid_for((int64_t)d->B * d->HW * (d->Cpad >> 2))), dim3(256), 0, (hipStream_t)s, *d);
+    hipLaunchKernelGGL(pack_kernel, dim3(grid_for((int64_t)d->B * d->HW * (d->Cpad >> 2), MISC_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d);
     return frido_check_launch("pack");
 }
 
 extern "C" int frido_relayout(const FridoRelayout* d, frido_stream_t s) {
     FRIDO_REQUIRE(d && d->src && d->dst, "null pointer");
     FRIDO_REQUIRE(d->c0 + d->Cuse <= d->Csrc && d->d0 + d->Cuse <= d->Cdst && d->Cuse > 0, "bad channel slice");
-    hipLaunchKernelGGL(relayout_kernel, dim3(grid_for((int64_t)d->B * d->HW * d->Cuse)), dim3(256), 0, (hipStream_t)s, *d);
+    hipLaunchKernelGGL(relayout_kernel, dim3(grid_for((int64_t)d->B * d->HW * d->Cuse, MISC_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d);
     return frido_check_launch("relayout");
 }
 
@@ -442,7 +439,7 @@ extern "C" int frido_sampler_step(const FridoSamplerStep* d, frido_stream_t s) {
                       "ancestral step: 16-byte aligned state, outputs and noise tape");
         FRIDO_REQUIRE(!d->noise || (d->noise_c0 >= 0 && d->noise_c0 <= d->start && d->noise_C == d->Cx - d->noise_c0),
                       "ancestral step: the noise tape spans channels [noise_c0, Cx) with noise_c0 <= start");
-        hipLaunchKernelGGL(ancestral_step_kernel, dim3(grid_for(((int64_t)d->B * d->HW * d->Cx) >> 2, 2048)), dim3(256), 0, (hipStream_t)s, *d);
+        hipLaunchKernelGGL(ancestral_step_kernel, dim3(grid_for(((int64_t)d->B * d->HW * d->Cx) >> 2, STEP_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d);
         return frido_check_launch("sampler_step (ancestral)");
     }
     FRIDO_REQUIRE(d->nch <= 12, "bad channel range");
@@ -450,7 +447,7 @@ extern "C" int frido_sampler_step(const FridoSamplerStep* d, frido_stream_t s) {
     FRIDO_REQUIRE(!d->hist_mode || (d->hist_ring && d->step && d->hist_stride >= (int64_t)d->B * d->HW * d->nch &&
                                     (d->hist_mode == 1 || d->hist_mode == 3) && !d->hist1 && !d->eps_out),
                   "hist ring: needs the device step counter, a [4][hist_stride] buffer and no explicit history pointers");
-    hipLaunchKernelGGL(sampler_step_kernel, dim3(grid_for((int64_t)d->B * d->HW, 2048)), dim3(256), 0, (hipStream_t)s, *d);
+    hipLaunchKernelGGL(sampler_step_kernel, dim3(grid_for((int64_t)d->B * d->HW, STEP_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d);
     return frido_check_launch("sampler_step");
 }
 
@@ -459,14 +456,14 @@ extern "C" int frido_handoff(const FridoHandoff* d, frido_stream_t s) {
     FRIDO_REQUIRE(d->levels >= 1 && d->levels <= 2, "hand-off supports 2x2 and 4x4 block means");
     FRIDO_REQUIRE(d->H % (1 << d->levels) == 0 && d->W % (1 << d->levels) == 0 && d->c1 > d->c0 && d->c1 <= d->Cx, "bad geometry");
     const int bs = 1 << d->levels;
-    hipLaunchKernelGGL(handoff_kernel, dim3(grid_for((int64_t)d->B * (d->H / bs) * (d->W / bs) * (d->c1 - d->c0))), dim3(256),
+    hipLaunchKernelGGL(handoff_kernel, dim3(grid_for((int64_t)d->B * (d->H / bs) * (d->W / bs) * (d->c1 - d->c0), MISC_GRID_CAP)), dim3(256),
                        0, (hipStream_t)s, *d);
     return frido_check_launch("handoff");
 }
 
 extern "C" int frido_randn(const FridoRandn* d, frido_stream_t s) {
     FRIDO_REQUIRE(d && d->dst && d->n > 0 && d->per_sample > 0 && (d->per_sample & 3) == 0, "bad arguments");
-    hipLaunchKernelGGL(randn_kernel, dim3(grid_for((d->n + 3) >> 2)), dim3(256), 0, (hipStream_t)s, *d);
+    hipLaunchKernelGGL(randn_kernel, dim3(grid_for((d->n + 3) >> 2, MISC_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d);
     return frido_check_launch("randn");
 }
 
@@ -478,19 +475,19 @@ extern "C" int frido_step_add(const FridoStepAdd* d, frido_stream_t s) {
 
 extern "C" int frido_time_emb(const FridoTimeEmb* d, frido_stream_t s) {
     FRIDO_REQUIRE(d && d->t && d->out && d->n > 0 && d->dim >= 2, "bad arguments");
-    hipLaunchKernelGGL(time_emb_kernel, dim3(grid_for((int64_t)d->n * (d->dim / 2))), dim3(256), 0, (hipStream_t)s, *d);
+    hipLaunchKernelGGL(time_emb_kernel, dim3(grid_for((int64_t)d->n * (d->dim / 2), MISC_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d);
     return frido_check_launch("time_emb");
 }
 
 extern "C" int frido_convt(const FridoConvT* d, frido_stream_t s) {
     FRIDO_REQUIRE(d && d->src && d->dst && d->weight && d->Cin > 0 && d->Cout > 0 && d->B > 0, "bad arguments");
-    hipLaunchKernelGGL(convt_kernel, dim3(grid_for((int64_t)d->B * d->h * d->w * 4 * d->Cout)), dim3(256), 0, (hipStream_t)s, *d);
+    hipLaunchKernelGGL(convt_kernel, dim3(grid_for((int64_t)d->B * d->h * d->w * 4 * d->Cout, MISC_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d);
     return frido_check_launch("convt");
 }
 
 extern "C" int frido_place(const FridoPlace* d, frido_stream_t s) {
     FRIDO_REQUIRE(d && d->src && d->dst && d->Cuse > 0 && d->c0 + d->Cuse <= d->Csrc && d->d0 + d->Cuse <= d->Cdst, "bad arguments");
-    hipLaunchKernelGGL(place_kernel, dim3(grid_for(((int64_t)d->B * d->Cuse * d->h * d->w) << (2 * d->up_shift))), dim3(256), 0,
+    hipLaunchKernelGGL(place_kernel, dim3(grid_for(((int64_t)d->B * d->Cuse * d->h * d->w) << (2 * d->up_shift), MISC_GRID_CAP)), dim3(256), 0,
                        (hipStream_t)s, *d);
     return frido_check_launch("place");
 }
@@ -498,13 +495,13 @@ extern "C" int frido_place(const FridoPlace* d, frido_stream_t s) {
 extern "C" int frido_embed(const FridoEmbed* d, frido_stream_t s) {
     FRIDO_REQUIRE(d && d->tokens && d->tok && d->out && d->rows > 0 && d->n > 0 && (d->D & 3) == 0 && d->vocab > 0,
                   "bad arguments");
-    hipLaunchKernelGGL(embed_kernel, dim3(grid_for((int64_t)d->rows * (d->D >> 2))), dim3(256), 0, (hipStream_t)s, *d);
+    hipLaunchKernelGGL(embed_kernel, dim3(grid_for((int64_t)d->rows * (d->D >> 2), MISC_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d);
     return frido_check_launch("embed");
 }
 
 extern "C" int frido_to_u8(const FridoToU8* d, frido_stream_t s) {
     FRIDO_REQUIRE(d && d->src && d->dst && d->n > 0, "bad arguments");
-    hipLaunchKernelGGL(to_u8_kernel, dim3(grid_for(d->n)), dim3(256), 0, (hipStream_t)s, *d);
+    hipLaunchKernelGGL(to_u8_kernel, dim3(grid_for(d->n, MISC_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d);
     return frido_check_launch("to_u8");
 }
 
@@ -517,6 +514,6 @@ extern "C" int frido_copy(const FridoCopy* d, frido_stream_t s) {
 
 extern "C" int frido_fill(const FridoFill* d, frido_stream_t s) {
     FRIDO_REQUIRE(d && d->dst && d->n > 0, "bad arguments");
-    hipLaunchKernelGGL(fill_kernel, dim3(grid_for(d->n)), dim3(256), 0, (hipStream_t)s, *d);
+    hipLaunchKernelGGL(fill_kernel, dim3(grid_for(d->n, MISC_GRID_CAP)), dim3(256), 0, (hipStream_t)s, *d);
     return frido_check_launch("fill");
 }

@@ -876,11 +876,6 @@ __global__ __launch_bounds__(256) void geglu_kernel(const FridoGeglu d) {
     status_raise(sat);
 }
 
-inline int grid_for(int64_t work_items, int cap = 4096) {
-    int64_t b = (work_items + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 }  // namespace
 
 extern "C" int frido_gn_stats(const FridoGnStats* d, frido_stream_t s) {
@@ -1012,6 +1007,6 @@ extern "C" int frido_l2norm(const FridoL2Norm* d, frido_stream_t s) {
 extern "C" int frido_geglu(const FridoGeglu* d, frido_stream_t s) {
     FRIDO_REQUIRE(d && d->x && d->out_op, "null pointer");
     FRIDO_REQUIRE((d->H & 3) == 0 && d->rows > 0, "H must be a multiple of 4");
-    hipLaunchKernelGGL(geglu_kernel, dim3(grid_for((int64_t)d->rows * (d->H >> 2))), dim3(256), 0, (hipStream_t)s, *d);
+    hipLaunchKernelGGL(geglu_kernel, dim3(grid_for((int64_t)d->rows * (d->H >> 2), 4096)), dim3(256), 0, (hipStream_t)s, *d);
     return frido_check_launch("geglu");
 }

@@ -34,44 +34,61 @@ int frido_check_launch(const char* what) {
     return FRIDO_OK;
 }
 
+// ---- the op table: the ONE place that ties an op kind to its launcher and its descriptor ----
+// ROW(kind suffix, launcher suffix, union member): FRIDO_OP_<kind> runs frido_<launcher>(&op.u.<member>, stream) and is sizeof(op.u.<member>)
+// bytes long.  Rows stand in the enum's order.  Two kinds share another kind's descriptor (GN_FUSED: gn_apply, ATTN_FLASH: attn_small);
+// SYNC has no launcher -- run_prog orders the streams itself -- and only a size.  run_one and frido_sizeof_desc are both generated from
+// this list, and a kind of include/frido_hip.h without a row fails the build below.
+#define FRIDO_OP_TABLE(ROW, ROW_NO_LAUNCHER)                      \
+    ROW(GEMM, gemm, gemm)                                         \
+    ROW(GN_STATS, gn_stats, gn_stats)                             \
+    ROW(GN_APPLY, gn_apply, gn_apply)                             \
+    ROW(LAYERNORM, layernorm, layernorm)                          \
+    ROW(SOFTMAX, softmax, softmax)                                \
+    ROW(GEGLU, geglu, geglu)                                      \
+    ROW(PACK, pack, pack)                                         \
+    ROW(RELAYOUT, relayout, relayout)                             \
+    ROW(VQ, vq, vq)                                               \
+    ROW(SAMPLER_STEP, sampler_step, sampler_step)                 \
+    ROW(HANDOFF, handoff, handoff)                                \
+    ROW(RANDN, randn, randn)                                      \
+    ROW(STEP_ADD, step_add, step_add)                             \
+    ROW(FILL, fill, fill)                                         \
+    ROW(TIME_EMB, time_emb, time_emb)                             \
+    ROW(CONVT, convt, convt)                                      \
+    ROW(PLACE, place, place)                                      \
+    ROW(EMBED, embed, embed)                                      \
+    ROW(TO_U8, to_u8, to_u8)                                      \
+    ROW(ATTN_SMALL, attn_small, attn_small)                       \
+    ROW(GN_FUSED, gn_fused, gn_apply)                             \
+    ROW(COPY, copy, copy)                                         \
+    ROW(ATTN_FLASH, attn_flash, attn_small)                       \
+    ROW_NO_LAUNCHER(SYNC, sync)                                   \
+    ROW(L2NORM, l2norm, l2norm)                                   \
+    ROW(ATTN_MH, attn_mh, attn_mh)                                \
+    ROW(UNFOLD, unfold, unfold)                                   \
+    ROW(FOLD, fold, fold)                                         \
+    ROW(QSAMPLE, qsample, qsample)                                \
+    ROW(DIFFUSION_LOSS, diffusion_loss, diffusion_loss)           \
+    ROW(VQ_COMMIT_LOSS, vq_commit_loss, vq_commit_loss)           \
+    ROW(DPM_STEP, dpm_step, dpm_step)                             \
+    ROW(KEEP_BLEND, keep_blend, keep_blend)                       \
+    ROW(INVERT_STEP, invert_step, invert_step)                    \
+    ROW(GUIDANCE_COMPOSE, guidance_compose, guidance_compose)
+
+#define COUNT_ROW(...) +1
+static_assert(0 FRIDO_OP_TABLE(COUNT_ROW, COUNT_ROW) == FRIDO_OP__COUNT - 1, "every op kind of include/frido_hip.h needs one row in FRIDO_OP_TABLE");
+#undef COUNT_ROW
+
 namespace {
 
 int run_one(const FridoOp& op, frido_stream_t s) {
     switch (op.kind) {
-        case FRIDO_OP_GEMM: return frido_gemm(&op.u.gemm, s);
-        case FRIDO_OP_GN_STATS: return frido_gn_stats(&op.u.gn_stats, s);
-        case FRIDO_OP_GN_APPLY: return frido_gn_apply(&op.u.gn_apply, s);
-        case FRIDO_OP_LAYERNORM: return frido_layernorm(&op.u.layernorm, s);
-        case FRIDO_OP_SOFTMAX: return frido_softmax(&op.u.softmax, s);
-        case FRIDO_OP_GEGLU: return frido_geglu(&op.u.geglu, s);
-        case FRIDO_OP_PACK: return frido_pack(&op.u.pack, s);
-        case FRIDO_OP_RELAYOUT: return frido_relayout(&op.u.relayout, s);
-        case FRIDO_OP_VQ: return frido_vq(&op.u.vq, s);
-        case FRIDO_OP_SAMPLER_STEP: return frido_sampler_step(&op.u.sampler_step, s);
-        case FRIDO_OP_HANDOFF: return frido_handoff(&op.u.handoff, s);
-        case FRIDO_OP_RANDN: return frido_randn(&op.u.randn, s);
-        case FRIDO_OP_STEP_ADD: return frido_step_add(&op.u.step_add, s);
-        case FRIDO_OP_FILL: return frido_fill(&op.u.fill, s);
-        case FRIDO_OP_TIME_EMB: return frido_time_emb(&op.u.time_emb, s);
-        case FRIDO_OP_CONVT: return frido_convt(&op.u.convt, s);
-        case FRIDO_OP_PLACE: return frido_place(&op.u.place, s);
-        case FRIDO_OP_EMBED: return frido_embed(&op.u.embed, s);
-        case FRIDO_OP_TO_U8: return frido_to_u8(&op.u.to_u8, s);
-        case FRIDO_OP_ATTN_SMALL: return frido_attn_small(&op.u.attn_small, s);
-        case FRIDO_OP_GN_FUSED: return frido_gn_fused(&op.u.gn_apply, s);
-        case FRIDO_OP_COPY: return frido_copy(&op.u.copy, s);
-        case FRIDO_OP_ATTN_FLASH: return frido_attn_flash(&op.u.attn_small, s);
-        case FRIDO_OP_L2NORM: return frido_l2norm(&op.u.l2norm, s);
-        case FRIDO_OP_ATTN_MH: return frido_attn_mh(&op.u.attn_mh, s);
-        case FRIDO_OP_UNFOLD: return frido_unfold(&op.u.unfold, s);
-        case FRIDO_OP_FOLD: return frido_fold(&op.u.fold, s);
-        case FRIDO_OP_QSAMPLE: return frido_qsample(&op.u.qsample, s);
-        case FRIDO_OP_DIFFUSION_LOSS: return frido_diffusion_loss(&op.u.diffusion_loss, s);
-        case FRIDO_OP_VQ_COMMIT_LOSS: return frido_vq_commit_loss(&op.u.vq_commit_loss, s);
-        case FRIDO_OP_DPM_STEP: return frido_dpm_step(&op.u.dpm_step, s);
-        case FRIDO_OP_KEEP_BLEND: return frido_keep_blend(&op.u.keep_blend, s);
-        case FRIDO_OP_INVERT_STEP: return frido_invert_step(&op.u.invert_step, s);
-        case FRIDO_OP_GUIDANCE_COMPOSE: return frido_guidance_compose(&op.u.guidance_compose, s);
+#define LAUNCH_CASE(KIND, launcher, member) case FRIDO_OP_##KIND: return frido_##launcher(&op.u.member, s);
+#define NO_CASE(KIND, member)
+        FRIDO_OP_TABLE(LAUNCH_CASE, NO_CASE)
+#undef LAUNCH_CASE
+#undef NO_CASE
         default:
             frido_set_error("frido_run: unknown op kind %d", op.kind);
             return FRIDO_EINVAL;
@@ -129,21 +146,22 @@ constexpr int GEMM_PAIRED = 1 << 28;
 
 bool pair_head(const FridoOp& op) { return op.kind == FRIDO_OP_GEMM && (op.u.gemm.flags & GEMM_PAIRED); }
 
-// the head's partner must be the next op, a GEMM on the same stream; nothing is launched otherwise
-int pair_check(const FridoOp* ops, int32_t n, int32_t i) {
-    if (i + 1 >= n || ops[i + 1].kind != FRIDO_OP_GEMM || ops[i + 1].stream != ops[i].stream) {
-        frido_set_error("op %d (kind %d): a paired GEMM (flags bit 28) must be followed by a FRIDO_OP_GEMM on the same stream", i, ops[i].kind);
-        return FRIDO_EINVAL;
-    }
+// Every head's partner must be the next op, a GEMM on the same stream: a malformed pair fails the program before its first launch.
+// (The partner's own bit 28, if set, means nothing.)
+int check_pairs(const FridoOp* ops, int32_t n) {
+    for (int32_t i = 0; i < n; ++i)
+        if (pair_head(ops[i])) {
+            if (i + 1 >= n || ops[i + 1].kind != FRIDO_OP_GEMM || ops[i + 1].stream != ops[i].stream) {
+                frido_set_error("op %d (kind %d): a paired GEMM (flags bit 28) must be followed by a FRIDO_OP_GEMM on the same stream", i, ops[i].kind);
+                return FRIDO_EINVAL;
+            }
+            ++i;
+        }
     return FRIDO_OK;
 }
 
 int run_prog(const FridoOp* ops, int32_t n, frido_stream_t s) {
-    for (int32_t i = 0; i < n; ++i)       // a malformed pair fails the program before its first launch
-        if (pair_head(ops[i])) {
-            if (const int rc = pair_check(ops, n, i)) return rc;
-            ++i;                          // (the partner's own bit 28, if set, means nothing)
-        }
+    if (const int rc = check_pairs(ops, n)) return rc;
     for (int32_t i = 0; i < n; ++i) {
         int rc;
         const int32_t i0 = i;
@@ -191,11 +209,7 @@ extern "C" int frido_run_timed(const FridoOp* ops, int32_t n, frido_stream_t s, 
         frido_set_error("frido_run_timed: bad arguments");
         return FRIDO_EINVAL;
     }
-    for (int32_t i = 0; i < n; ++i)
-        if (pair_head(ops[i])) {
-            if (const int rc = pair_check(ops, n, i)) return rc;
-            ++i;
-        }
+    if (const int rc = check_pairs(ops, n)) return rc;
     std::vector<hipEvent_t> ev(n + 1);
     for (auto& e : ev)
         if (hipEventCreate(&e) != hipSuccess) return FRIDO_EHIP;
@@ -346,41 +360,11 @@ extern "C" int frido_x3_plane_format(void) { return FRIDO_X3_F16 ? 1 : 0; }
 extern "C" int frido_sizeof_op(void) { return (int)sizeof(FridoOp); }
 extern "C" int frido_sizeof_desc(int32_t kind) {
     switch (kind) {
-        case FRIDO_OP_GEMM: return sizeof(FridoGemm);
-        case FRIDO_OP_GN_STATS: return sizeof(FridoGnStats);
-        case FRIDO_OP_GN_APPLY: return sizeof(FridoGnApply);
-        case FRIDO_OP_LAYERNORM: return sizeof(FridoLayerNorm);
-        case FRIDO_OP_SOFTMAX: return sizeof(FridoSoftmax);
-        case FRIDO_OP_GEGLU: return sizeof(FridoGeglu);
-        case FRIDO_OP_PACK: return sizeof(FridoPack);
-        case FRIDO_OP_RELAYOUT: return sizeof(FridoRelayout);
-        case FRIDO_OP_VQ: return sizeof(FridoVq);
-        case FRIDO_OP_SAMPLER_STEP: return sizeof(FridoSamplerStep);
-        case FRIDO_OP_HANDOFF: return sizeof(FridoHandoff);
-        case FRIDO_OP_RANDN: return sizeof(FridoRandn);
-        case FRIDO_OP_STEP_ADD: return sizeof(FridoStepAdd);
-        case FRIDO_OP_FILL: return sizeof(FridoFill);
-        case FRIDO_OP_TIME_EMB: return sizeof(FridoTimeEmb);
-        case FRIDO_OP_CONVT: return sizeof(FridoConvT);
-        case FRIDO_OP_PLACE: return sizeof(FridoPlace);
-        case FRIDO_OP_EMBED: return sizeof(FridoEmbed);
-        case FRIDO_OP_TO_U8: return sizeof(FridoToU8);
-        case FRIDO_OP_ATTN_SMALL: return sizeof(FridoAttnSmall);
-        case FRIDO_OP_GN_FUSED: return sizeof(FridoGnApply);
-        case FRIDO_OP_COPY: return sizeof(FridoCopy);
-        case FRIDO_OP_ATTN_FLASH: return sizeof(FridoAttnSmall);
-        case FRIDO_OP_SYNC: return sizeof(FridoSync);
-        case FRIDO_OP_L2NORM: return sizeof(FridoL2Norm);
-        case FRIDO_OP_ATTN_MH: return sizeof(FridoAttnMh);
-        case FRIDO_OP_UNFOLD: return sizeof(FridoUnfold);
-        case FRIDO_OP_FOLD: return sizeof(FridoFold);
-        case FRIDO_OP_QSAMPLE: return sizeof(FridoQSample);
-        case FRIDO_OP_DIFFUSION_LOSS: return sizeof(FridoDiffusionLoss);
-        case FRIDO_OP_VQ_COMMIT_LOSS: return sizeof(FridoVqCommitLoss);
-        case FRIDO_OP_DPM_STEP: return sizeof(FridoDpmStep);
-        case FRIDO_OP_KEEP_BLEND: return sizeof(FridoKeepBlend);
-        case FRIDO_OP_INVERT_STEP: return sizeof(FridoInvertStep);
-        case FRIDO_OP_GUIDANCE_COMPOSE: return sizeof(FridoGuidanceCompose);
+#define SIZE_CASE(KIND, launcher, member) case FRIDO_OP_##KIND: return (int)sizeof(FridoOp::u.member);
+#define SIZE_CASE_NO_LAUNCHER(KIND, member) case FRIDO_OP_##KIND: return (int)sizeof(FridoOp::u.member);
+        FRIDO_OP_TABLE(SIZE_CASE, SIZE_CASE_NO_LAUNCHER)
+#undef SIZE_CASE
+#undef SIZE_CASE_NO_LAUNCHER
         default: return -1;
     }
 }

@@ -1,29 +1,13 @@
 // The codebook / commitment loss of the MS-VQGAN (taming/models/msvqgan.py:116-154 MSFPNVQModel.encode: emb_loss = sum(emb_loss_ms);
 // taming/modules/vqvae/quantize.py:286-291 VectorQuantizer2.forward: mean((z_q - z)^2) twice, weighted 1 and beta).
-// Plain f32 / f64 arithmetic: no operand planes, so no status word (common.h is not included on purpose -- it would register one) and
+// Plain f32 / f64 arithmetic: no operand planes, so no status word (launch.h alone: common.h is not included on purpose -- it would register one) and
 // the two builds of the library compile the same code.  Bandwidth-bound and small: the maps are the e-channel latents of every scale.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "frido_hip.h"
-
-void frido_set_error(const char* fmt, ...);
-int frido_check_launch(const char* what);
-
-#define VQL_REQUIRE(cond, msg)                                              \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            frido_set_error("%s: %s (%s)", __func__, msg, #cond);           \
-            return FRIDO_EINVAL;                                            \
-        }                                                                   \
-    } while (0)
+#include "launch.h"
 
 namespace {
 
 constexpr int MAXS = FRIDO_VQLOSS_MAX_SCALES, MAXWG = FRIDO_VQLOSS_MAX_WG;
 constexpr int64_t UNITS_PER_WG = 256 * 16;      // a workgroup is worth starting for 16 units per thread
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // Workgroups of a scale: a function of the scale's OWN size only, so its partials -- and its mean -- do not depend on which other scales
 // share the launch.
@@ -103,18 +87,18 @@ __global__ __launch_bounds__(64) void vqloss_finish_kernel(const FridoVqCommitLo
 }  // namespace
 
 extern "C" int frido_vq_commit_loss(const FridoVqCommitLoss* d, frido_stream_t s) {
-    VQL_REQUIRE(d && d->partials && d->out && d->emb_loss, "null pointer");
-    VQL_REQUIRE(d->n_scales >= 1 && d->n_scales <= MAXS, "1 to 4 scales");
-    VQL_REQUIRE(d->beta == d->beta, "beta is NaN");
-    VQL_REQUIRE(aligned16(d->partials), "the partials workspace must be 16-byte aligned");
+    FRIDO_REQUIRE(d && d->partials && d->out && d->emb_loss, "null pointer");
+    FRIDO_REQUIRE(d->n_scales >= 1 && d->n_scales <= MAXS, "1 to 4 scales");
+    FRIDO_REQUIRE(d->beta == d->beta, "beta is NaN");
+    FRIDO_REQUIRE(aligned16(d->partials), "the partials workspace must be 16-byte aligned");
     Split sp = {};
     for (int k = 0; k < d->n_scales; ++k) {
-        VQL_REQUIRE(d->z[k] && d->zq[k], "null pointer");
-        VQL_REQUIRE(d->npix[k] > 0 && d->C[k] > 0 && d->e[k] > 0, "npix, C and e must be positive");
-        VQL_REQUIRE(d->c0[k] >= 0 && (int64_t)d->c0[k] + d->e[k] <= d->C[k], "the channel slice must lie inside [0, C]");
-        VQL_REQUIRE(d->npix[k] <= ((int64_t)1 << 40), "npix is out of range");
+        FRIDO_REQUIRE(d->z[k] && d->zq[k], "null pointer");
+        FRIDO_REQUIRE(d->npix[k] > 0 && d->C[k] > 0 && d->e[k] > 0, "npix, C and e must be positive");
+        FRIDO_REQUIRE(d->c0[k] >= 0 && (int64_t)d->c0[k] + d->e[k] <= d->C[k], "the channel slice must lie inside [0, C]");
+        FRIDO_REQUIRE(d->npix[k] <= ((int64_t)1 << 40), "npix is out of range");
         const bool vec = d->C[k] % 4 == 0 && d->c0[k] % 4 == 0 && d->e[k] % 4 == 0;
-        VQL_REQUIRE(!vec || (aligned16(d->z[k]) && aligned16(d->zq[k])), "16-byte accesses: z and zq must be 16-byte aligned");
+        FRIDO_REQUIRE(!vec || (aligned16(d->z[k]) && aligned16(d->zq[k])), "16-byte accesses: z and zq must be 16-byte aligned");
         sp.vec[k] = vec ? 1 : 0;
         sp.wg0[k + 1] = sp.wg0[k] + wgs_of(d->npix[k] * (d->e[k] / (vec ? 4 : 1)));
     }
