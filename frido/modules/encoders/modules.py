@@ -1,2 +1,3 @@
-"""`frido.modules.encoders.modules` import path (cond_stage_config.target) -> HIP-backed BERTEmbedder; CLIP stand-in."""
-from frido_amd.models import BERTEmbedder, FrozenCLIPTextEmbedder  # noqa: F401
+"""`frido.modules.encoders.modules` import path (cond_stage_config.target) -> the HIP-backed embedders: BERTEmbedder, the CLIP text tower
+and the CLIP image tower."""
+from frido_amd.models import BERTEmbedder, FrozenCLIPTextEmbedder, FrozenClipImageEmbedder  # noqa: F401

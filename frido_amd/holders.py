@@ -372,3 +372,50 @@ def build_clip_text_params(root, embed_dim, context_length, vocab_size, width, h
     m.text_projection = _p(width, embed_dim)
     m.logit_scale = nn.Parameter(torch.empty(()), requires_grad=False)
     root.model = m
+
+
+# ---- FrozenClipImageEmbedder.model.visual = OpenAI CLIP's VisionTransformer (clip/model.py VisionTransformer.__init__) ------------------
+CLIP_VISUAL_ARCH = {      # version -> (embed_dim, image_resolution, vision_layers, vision_width, vision_patch_size); heads = width // 64
+    "ViT-B/32": (512, 224, 12, 768, 32),
+    "ViT-B/16": (512, 224, 12, 768, 16),
+    "ViT-L/14": (768, 224, 24, 1024, 14),
+    "ViT-L/14@336px": (768, 336, 24, 1024, 14),
+}
+CLIP_RESNET_VERSIONS = ("RN50", "RN101", "RN50x4", "RN50x16", "RN50x64")      # clip.available_models(): ModifiedResNet + attention pooling
+
+
+def build_clip_visual_params(root, embed_dim, resolution, layers, width, patch):
+    """Parameter tree of the image side of clip.model.CLIP under `root.model.visual` (state_dict keys `model.visual.conv1.weight`
+    -- no bias --, `model.visual.class_embedding`, `model.visual.positional_embedding`, `model.visual.ln_pre`,
+    `model.visual.transformer.resblocks.N.{ln_1,attn.in_proj_*,attn.out_proj,ln_2,mlp.c_fc,mlp.c_proj}`, `model.visual.ln_post`,
+    `model.visual.proj`): the mirror image of build_clip_text_params -- a full CLIP state_dict's `model.visual.*` keys load into it and
+    its text keys (`model.token_embedding.weight`, `model.transformer.*`, `model.ln_final.*`, `model.text_projection`,
+    `model.logit_scale`, `model.positional_embedding`) are simply unexpected keys of a strict=False load."""
+    if resolution % patch:
+        raise ValueError(f"CLIP image tower: the resolution {resolution} is not a whole number of {patch} x {patch} patches")
+    v = Nop()
+    v.conv1 = Nop()
+    v.conv1.weight = _p(width, 3, patch, patch)
+    v.class_embedding = _p(width)
+    v.positional_embedding = _p((resolution // patch) ** 2 + 1, width)
+    v.ln_pre = Affine(width)
+    blocks = []
+    for _ in range(layers):
+        blk = Nop()
+        blk.ln_1, blk.ln_2 = Affine(width), Affine(width)
+        attn = Nop()
+        attn.in_proj_weight, attn.in_proj_bias = _p(3 * width, width), _p(3 * width)
+        attn.out_proj = Lin(width, width)
+        blk.attn = attn
+        mlp = Nop()
+        mlp.c_fc, mlp.c_proj = Lin(width, 4 * width), Lin(4 * width, width)
+        blk.mlp = mlp
+        blocks.append(blk)
+    tr = Nop()
+    tr.resblocks = seq(*blocks)
+    v.transformer = tr
+    v.ln_post = Affine(width)
+    v.proj = _p(width, embed_dim)
+    m = Nop()
+    m.visual = v
+    root.model = m

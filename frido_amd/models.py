@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import _lib, autoplanes, config, holders, runtime, schedules
 from ._lib import FridoHipError
-from .engine import current_stream_ptr, lru_entry
+from .engine import current_stream_ptr, lru_entry, own_stream, require_gpu
 
 try:  # pytorch-lightning is optional (absent in this image): keep the LightningModule base when it exists
     import pytorch_lightning as _pl
@@ -615,6 +615,132 @@ class FrozenCLIPTextEmbedder(_TextTower):
         if z.ndim == 2:
             z = z[:, None, :]
         return z.expand(-1, self.n_repeat, -1).contiguous()      # repeat(z, 'b 1 d -> b k d', k=n_repeat)
+
+
+class FrozenClipImageEmbedder(_Versioned, nn.Module):
+    """The third embedder of frido/modules/encoders/modules.py (:222-254): the image tower of OpenAI CLIP.  `forward` takes images
+    [B, 3, H, W] float32 in [-1, 1] on the GPU and returns `encode_image`'s [B, embed_dim] float32, NOT normalised, like the reference:
+    bicubic resize (align_corners=True) to the tower's resolution, CLIP's mean / std, then the VisionTransformer -- one HIP kernel
+    (csrc/vision.hip) in front of the tower's program (clip_plan.ClipImagePlan), both replayed as ONE captured graph per input shape
+    (B, H, W); the plans are kept least-recently-used like the text towers'.  The weights live under `self.model.visual` with OpenAI
+    CLIP's state_dict names: a full CLIP state_dict loads with strict=False (its text keys are the unexpected ones).
+    `model`: a ViT version of holders.CLIP_VISUAL_ARCH; `arch=(embed_dim, resolution, layers, width, patch)` builds a custom tower
+    (heads = width // 64, clip/model.py).  Refused by name: jit=True, antialias=True (kornia's pre-blur is not restated here), the
+    ResNet versions (ModifiedResNet + attention pooling).  `preprocess(x)` returns the resized, normalised [B, 3, res, res] image the
+    tower sees -- the kernel's output re-laid by torch, for inspection and tests."""
+
+    _what = "FrozenClipImageEmbedder"
+
+    def __init__(self, model, jit=False, device="cuda", antialias=False, *, arch=None, precision=None):
+        super().__init__()
+        if jit:
+            raise NotImplementedError("FrozenClipImageEmbedder: jit=True loads a TorchScript archive of the `clip` package; the HIP "
+                                      "engine runs the tower from its state_dict only (pass jit=False)")
+        if antialias:
+            raise NotImplementedError("FrozenClipImageEmbedder: antialias=True (kornia's Gaussian pre-blur before the bicubic resize) is "
+                                      "not implemented; pass antialias=False, the reference's default")
+        if arch is None:
+            if model in holders.CLIP_RESNET_VERSIONS:
+                raise NotImplementedError(f"FrozenClipImageEmbedder: '{model}' is a ResNet CLIP tower (ModifiedResNet with attention "
+                                          f"pooling), which is not implemented; the ViT versions are {sorted(holders.CLIP_VISUAL_ARCH)}")
+            if model not in holders.CLIP_VISUAL_ARCH:
+                raise NotImplementedError(f"FrozenClipImageEmbedder: unknown CLIP version '{model}' (known: "
+                                          f"{sorted(holders.CLIP_VISUAL_ARCH)}); pass arch=(embed_dim, resolution, layers, width, patch)")
+            arch = holders.CLIP_VISUAL_ARCH[model]
+        self.arch = tuple(int(a) for a in arch)
+        embed_dim, res, layers, width, patch = self.arch
+        if width % 64:
+            raise ValueError(f"FrozenClipImageEmbedder: width {width} must be a multiple of 64 (clip/model.py: heads = width // 64)")
+        if width > 1024:
+            raise ValueError(f"FrozenClipImageEmbedder: width {width} exceeds 1024, the widest row of the LayerNorm kernel "
+                             "(csrc/norm.hip frido_layernorm: C <= 1024); every published ViT tower up to ViT-L fits")
+        self.version, self.device, self.antialias, self.precision = model, device, antialias, precision
+        holders.build_clip_visual_params(self, *self.arch)      # ValueError: a resolution that is no whole number of patches
+        self.register_buffer("mean", torch.Tensor([0.48145466, 0.4578275, 0.40821073]), persistent=False)
+        self.register_buffer("std", torch.Tensor([0.26862954, 0.26130258, 0.27577711]), persistent=False)
+        self._init_versioning()
+
+    def _init_versioning(self):
+        super()._init_versioning()
+        self._plans = {}
+
+    def invalidate(self):
+        self._rt = None
+        self._plans = {}
+
+    def _check(self, x):
+        if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3 or 0 in x.shape:
+            got = tuple(x.shape) if torch.is_tensor(x) else type(x).__name__
+            raise ValueError(f"FrozenClipImageEmbedder: images must be a [B, 3, H, W] tensor in [-1, 1], got {got}")
+        _on_gpu(self._what, self, x)
+
+    def _norm(self):
+        return [float(v) for v in self.mean.tolist()], [float(v) for v in self.std.tolist()]
+
+    @torch.no_grad()
+    @_lib.with_planes
+    def preprocess(self, x):
+        """[B, 3, H, W] in [-1, 1] -> the [B, 3, res, res] image the tower sees (encoders/modules.py:242-250 with antialias=False)."""
+        from . import vision
+        self._check(x)
+        _, res, _, _, P = self.arch
+        B, _, H, W = x.shape
+        g = res // P
+        require_gpu(x.device)
+        src = x.detach().float().contiguous()
+        dst = torch.empty(B * g * g, 3 * P * P, dtype=torch.float32, device=x.device)
+        mean, std = self._norm()
+        vision.clip_preprocess(vision.preprocess_desc(src.data_ptr(), dst.data_ptr(), B, H, W, res, P, mean, std), current_stream_ptr(x.device))
+        return dst.view(B, g, g, 3, P, P).permute(0, 3, 1, 4, 2, 5).reshape(B, 3, res, res)
+
+    def _make_plan(self, B, H, W, stream):
+        from .clip_plan import ClipImagePlan
+        embed_dim, res, layers, width, patch = self.arch
+        mean, std = self._norm()
+        plan = ClipImagePlan(self._rt, B=B, H=H, W=W, embed_dim=embed_dim, resolution=res, layers=layers, width=width, patch=patch,
+                             mean=mean, std=std, stream=stream)
+        plan.graph = None
+        return plan
+
+    def _capture(self, plan, sp):
+        """plan.graph: the preprocess launch and the tower's program as one hipGraph, captured on the stream `sp`."""
+        import ctypes
+        from .engine import Graph
+        L = _lib.lib()
+        _lib.check(L.frido_capture_begin(sp), "frido_capture_begin")
+        h = ctypes.c_void_p()
+        try:
+            plan.launch(sp)
+        except Exception:
+            if L.frido_capture_end(sp, ctypes.byref(h)) == 0:      # a failed body still has to end its capture
+                L.frido_graph_destroy(h)
+            raise
+        _lib.check(L.frido_capture_end(sp, ctypes.byref(h)), "frido_capture_end")
+        plan.graph = Graph(h, plan)
+        self.graph_captures += 1
+
+    graph_captures = 0      # graphs captured so far (one per input shape in the cache; tests read it)
+
+    @torch.no_grad()
+    @_lib.with_planes
+    def forward(self, x):
+        self._check(x)
+        dev = next(self.parameters()).device
+        B, _, H, W = x.shape
+        with own_stream(self, dev) as sp:
+            if self._rt is None:
+                self._plans = {}
+                self._rt = runtime.module_builder(self, dev, self.precision)
+
+            def build():      # like _cached_plan; an evicted plan's graph may still be running on this stream: wait for it first
+                with self._rt.persist_scope() as owned:
+                    return self._make_plan(B, H, W, sp), owned
+            plan = lru_entry(self._plans, (B, H, W), PLAN_CACHE_SIZE, build, before_evict=self._stream.synchronize)[0]
+            plan.x_in.copy_(x)
+            if plan.graph is None:
+                self._capture(plan, sp)
+            plan.graph.launch(sp)
+            return plan.out.clone()
 
 
 def _first(cond, n):

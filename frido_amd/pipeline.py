@@ -156,3 +156,42 @@ def invert_images(model, images, cond, *, S, t_start=None, strength=None, scale=
         from . import _lib
         _lib.warn_on_status("invert_images")
     return all_gather_images(x_inv, total=total) if gather else x_inv
+
+
+def _l2norm_rows(z):
+    """z / ||z||_2 per row of a [B, C] f32 tensor on the GPU, by the library's row kernel (FRIDO_OP_L2NORM) on the current stream."""
+    from .engine import Prog, current_stream_ptr
+    z = z.float().contiguous()
+    out = torch.empty_like(z)
+    p = Prog(z.device, 2)
+    p.emit("FRIDO_OP_L2NORM", x=z.data_ptr(), out=out.data_ptr(), rows=z.shape[0], C=z.shape[1])
+    p.run(current_stream_ptr(z.device))
+    return out
+
+
+@torch.no_grad()
+def clip_score(image_embedder, text_embedder, images, text):
+    """Cosine between the CLIP embeddings of images and their captions: [B] float32 on the device, without leaving it.
+    image_embedder: a FrozenClipImageEmbedder; images [B, 3, H, W] in [-1, 1] on the GPU (what the decoders return).
+    text_embedder: a FrozenCLIPTextEmbedder of the same embed_dim; text: [B, n] token ids, or strings under that class's own rules.
+    Both embeddings are L2-normalised by the library's row kernel (the text tower's own when it was built with normalize=True);
+    the row dot product is one torch expression on [B, embed_dim].
+    CLIPScore (Hessel et al. 2021, "CLIPScore: A Reference-free Evaluation Metric for Image Captioning") is 2.5 * max(cos, 0) of the
+    value returned here, taken with a TRAINED CLIP.  No trained weights ship with this repository: the function computes the quantity
+    for whatever state_dict the two embedders hold, and nothing here claims a quality number.
+    Under torch.distributed every rank scores its own shard; gathering the scores is the caller's."""
+    from .models import FrozenCLIPTextEmbedder, FrozenClipImageEmbedder
+    if not isinstance(image_embedder, FrozenClipImageEmbedder):
+        raise ValueError(f"clip_score: image_embedder must be a FrozenClipImageEmbedder, got {type(image_embedder).__name__}")
+    if not isinstance(text_embedder, FrozenCLIPTextEmbedder):
+        raise ValueError(f"clip_score: text_embedder must be a FrozenCLIPTextEmbedder, got {type(text_embedder).__name__}")
+    if image_embedder.arch[0] != text_embedder.arch[0]:
+        raise ValueError(f"clip_score: the image tower embeds into {image_embedder.arch[0]} dimensions, the text tower into "
+                         f"{text_embedder.arch[0]}: the two are not halves of one CLIP")
+    zi = _l2norm_rows(image_embedder(images))
+    zt = text_embedder(text)
+    if not text_embedder.normalize:
+        zt = _l2norm_rows(zt)
+    if zt.shape != zi.shape:
+        raise ValueError(f"clip_score: {zi.shape[0]} images but {zt.shape[0]} captions")
+    return (zi * zt).sum(dim=-1)
