@@ -23,6 +23,10 @@ GEMM_PAIR = True
 # GEMM -> softmax -> GEMM chain fills the chip better than one workgroup per 64 queries (measured at B = 16: 256 keys x d = 576:
 # 37 us vs 49 us; 1024 keys x d = 384: 102 vs 82 us)
 ATTN_FLASH_MIN_KEYS = 512
+# test knob / A-B handle: a transformer block whose self-attention takes the d-split flash kernel hands that launch its cross-attention
+# and norm3 as well (FridoAttnSmall's cross tail, Builder.attention_chain).  Off: the two launches (flash, then short-key).
+ATTN_CHAIN = True
+ATTN_CHAIN_HEAD_DIMS = (256, 384)       # head widths whose d-split kernel carries the tail (csrc/flash.hip FDGeo::TAIL)
 
 
 class Builder:
@@ -655,6 +659,43 @@ class Builder:
                        oo_bs=Nq * d, ldoo=d, oo_lo=o.lo)
         p.free()
         return o
+
+    def attention_chain_ok(self, ldq, ldk, Nk, d, Nk2, ldk2):
+        """True where attention_chain applies: two-plane mode with an f32 stream, a self-attention that takes the d-split flash kernel
+        with its fused LayerNorm at a head width that carries the cross tail, and a context of at most 32 tokens."""
+        return bool(ATTN_CHAIN and self.nsplit == 2 and not self.stream_bf16 and d in ATTN_CHAIN_HEAD_DIMS and self._flash_ln_ok(d)
+                    and Nk >= ATTN_FLASH_MIN_KEYS and ldq % 8 == 0 and ldk % 8 == 0 and ldk2 % 8 == 0 and 1 <= Nk2 <= 32)
+
+    def attention_chain(self, q, ldq, k, ldk, vT, B, Nq, Nk, d, *, bias_ptr, residual, ln, k2, ldk2, vT2, Nk2, bias2_ptr, ln2,
+                        also_op=False, stream_dead=False):
+        """A transformer block's self-attention, norm2, cross-attention and norm3 in ONE flash launch (attention_chain_ok):
+            h2 = softmax(q k^T / sqrt(d)) v + bias + residual,  n2 = LayerNorm(h2; ln),
+            h3 = softmax(n2 k2^T / sqrt(d)) v2 + bias2 + h2,    n3 = LayerNorm(h3; ln2)
+        with h2 / n2 never leaving the kernel.  q, k, vT as in attention(); k2: operand rows [B][Nk2] (row stride ldk2), vT2: operand
+        [B][d][32] (zero beyond Nk2); ln, ln2 = (weight name, eps).  Returns the stream activation h3 with h3.ln_copy = n3 and, with
+        also_op, h3.op_copy; stream_dead as in attention(): with both copies produced the f32 rows of h3 are not stored
+        (h3.stream_skipped = True)."""
+        assert self.attention_chain_ok(ldq, ldk, Nk, d, Nk2, ldk2) and residual is not None and not getattr(residual, "bf16", False)
+        Np = rup(Nk, 32)
+        res = self.f32(B * Nq, d)
+        n3 = self.op(B * Nq, d)
+        res.ln_copy = n3
+        kw = dict(Q=q.ptr, q_lo=q.lo, ldq=ldq, K=k.ptr, k_lo=k.lo, k_bs=Nk * ldk, ldk=ldk, VT=vT.ptr, vt_lo=vT.lo, vt_bs=d * Np, ldvt=Np,
+                  B=B, Nq=Nq, Nk=Nk, d=d, dv=d, nsplit=self.nsplit, alpha=float(d) ** -0.5, residual=residual.ptr, ldr=residual.C,
+                  bias=bias_ptr, ln_w=self.bias(ln[0] + ".weight"), ln_b=self.bias(ln[0] + ".bias"), ln_eps=ln[1],
+                  K2=k2.ptr, k2_lo=k2.lo, k2_bs=Nk2 * ldk2, ldk2=ldk2, VT2=vT2.ptr, vt2_lo=vT2.lo, vt2_bs=d * 32, ldvt2=32, Nk2=Nk2,
+                  alpha2=float(d) ** -0.5, bias2=bias2_ptr, ln2_w=self.bias(ln2[0] + ".weight"), ln2_b=self.bias(ln2[0] + ".bias"),
+                  ln2_eps=ln2[1], ln2_op=n3.ptr, ln2_lo=n3.lo, ld_ln2=d)
+        if also_op:
+            o = self.op(B * Nq, d)
+            kw.update(out2_op=o.ptr, out2_lo=o.lo, ldo2=d)
+            res.op_copy = o
+        if stream_dead and also_op:
+            res.stream_skipped = True
+        else:
+            kw.update(out2_act=res.ptr, ld_act2=d)
+        self.prog.emit("FRIDO_OP_ATTN_FLASH", **kw)
+        return res
 
     def attention_heads(self, qkv, ldqkv, vT, B, N, heads, d, *, legacy=True, **one_head):
         """Self-attention core of the reference's AttentionBlock (pyunet.py:303-358) over N tokens per sample.  qkv: operand rows

@@ -410,6 +410,7 @@ int launch_attn(const FridoAttnSmall& d, hipStream_t s) {
 
 extern "C" int frido_attn_small(const FridoAttnSmall* d, frido_stream_t s) {
     FRIDO_REQUIRE(d && d->Q && d->K && d->VT && (d->out_op || d->out_act), "null pointer");
+    FRIDO_REQUIRE(!d->K2 && !d->VT2 && !d->Nk2 && !d->ln2_op && !d->out2_op && !d->out2_act, "cross tail (K2 ...) is served by frido_attn_flash only");
     FRIDO_REQUIRE(!d->out_act || ((d->ld_act & 3) == 0 && (d->ldr & 3) == 0), "stream strides must be multiples of 4");
     FRIDO_REQUIRE(d->B > 0 && d->Nq > 0 && (d->Nq & 15) == 0, "Nq must be a positive multiple of 16");
     FRIDO_REQUIRE(d->Nk > 0 && d->Nk <= 128 && d->ldvt >= d->Nk && d->ldvt <= 128 && (d->ldvt & 31) == 0, "Nk must be in [1, 128], ldvt a multiple of 32");

@@ -450,6 +450,10 @@ struct FDGeo {
     static constexpr int X0 = V0 + VBUF;                 // exchange buffer offset
     static constexpr int SMEM = X0 + XCH;
     static constexpr int KP = KS * 2, VP = D / 16;       // 1-KiB DMA pieces per plane
+    // the cross tail (FridoAttnSmall.K2) keeps h2 AND the planes of n2 in registers next to the K2 / V2^T fragments: d = 512 runs at
+    // 256 registers without it.  Its LDS words lie in the K ring (free once the main loop is over): no byte more than before.
+    static constexpr bool TAIL = D <= 384;
+    static_assert(!TAIL || KBUF >= XCH + 1024, "the tail's exchange words live in the first K buffer");
     static_assert(KS % 2 == 0 && CTH % 2 == 0 && SMEM <= 163840, "d-split geometry / LDS budget");
     static_assert(!KDB || KP % NW == 0, "the counted vmcnt wait of the double-buffered form needs every wave to issue the same number of K pieces");
 };
@@ -674,7 +678,14 @@ __global__ __launch_bounds__(512, 1) void flash_ds_kernel(const FridoAttnSmall d
 
     // ---- epilogue: lane holds O^T[c = 16 (hf CTH + ct) + 4 g + e][q = r] ----
     const float inv = 1.0f / l_run;
-    const bool ln = d.ln_op != nullptr;
+    // cross tail (FridoAttnSmall.K2): the stream form and its LayerNorm are computed whether or not they are stored
+    // (the pointer passes through an empty asm here, AFTER the main loop: the compiler then cannot unswitch the loop on it -- it built a
+    //  second copy of the whole kernel for tailed launches, with the tail's addresses hoisted above the loop and spilled -- so launches
+    //  with and without a tail run the same main loop)
+    const frido_bf16* k2_ptr = d.K2;
+    asm volatile("" : "+s"(k2_ptr));
+    const bool tail = G::TAIL && k2_ptr != nullptr;
+    const bool ln = d.ln_op != nullptr || tail;
     float lsum = 0.f;
     bool sat = false;
     if (q_ok) status_raise(false, g == 0 && hf == 0 && stat_bad(m_run, inv));
@@ -682,7 +693,7 @@ __global__ __launch_bounds__(512, 1) void flash_ds_kernel(const FridoAttnSmall d
     for (int c = 0; c < CTH; ++c) {
         const int col = (hf * CTH + c) * 16 + g * 4;
         float4 v = make_float4(o[c][0] * inv, o[c][1] * inv, o[c][2] * inv, o[c][3] * inv);
-        if (d.out_act) {
+        if (d.out_act || tail) {
             if (d.bias) {
                 const float4 bb = *reinterpret_cast<const float4*>(d.bias + col);
                 v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w;
@@ -692,7 +703,7 @@ __global__ __launch_bounds__(512, 1) void flash_ds_kernel(const FridoAttnSmall d
                 v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
             }
             const int64_t oo = grow * d.ld_act + col;
-            if (q_ok) {
+            if (q_ok && d.out_act) {
                 if (d.act_bf16)
                     *reinterpret_cast<uint2*>(reinterpret_cast<frido_bf16*>(d.out_act) + oo) =
                         make_uint2(f32_to_bf16_bits(v.x) | (f32_to_bf16_bits(v.y) << 16), f32_to_bf16_bits(v.z) | (f32_to_bf16_bits(v.w) << 16));
@@ -707,6 +718,37 @@ __global__ __launch_bounds__(512, 1) void flash_ds_kernel(const FridoAttnSmall d
             const float vv[4] = {v.x, v.y, v.z, v.w};
             store_op4(d.out_op, d.out_lo, NS, grow * d.ldo + col, vv);
             sat |= op_sat4(vv);
+        }
+    }
+    // The tail's K2 fragments (A operand of S2^T = K2 . n2^T over this wave's half of d) depend on nothing computed here: they are
+    // fetched NOW, straight from L2 (26 x 384 per sample), and land under the two barriers of the first LayerNorm.  Row 4 a + b of
+    // score fragment f is key 8 a + 4 f + b (the main loop's permutation); within a 32-deep step the 8 k-slots of lane group g are the
+    // channels 16 c + 4 g + e and 16 (c + 1) + 4 g + e -- the order in which the lane holds n2 -- as two 8-byte loads per plane.
+    bf16x8 k2f[G::TAIL ? CTH / 2 : 1][2][NS];          // [k-step][score fragment][plane]
+    // (the first K2E k-steps now; at d = 384 the last two go out once the LayerNorm's own parameters have left the registers)
+    constexpr int K2E = CTH / 2 <= 4 ? CTH / 2 : 2;
+    const frido_bf16* k2p[2] = {nullptr, nullptr};
+    auto load_k2 = [&](int ks) {
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+            for (int p = 0; p < NS; ++p) {
+                const frido_bf16* src = k2p[f] + (p ? d.k2_lo : 0) + ks * 32;
+                const uint2 a0 = *reinterpret_cast<const uint2*>(src), a1 = *reinterpret_cast<const uint2*>(src + 16);
+                k2f[ks][f][p] = __builtin_bit_cast(bf16x8, u32x4{a0.x, a0.y, a1.x, a1.y});
+            }
+    };
+    if constexpr (G::TAIL) {
+        if (tail) {
+            const frido_bf16* k2b = k2_ptr + (int64_t)z * d.k2_bs + hf * (D / 2) + g * 4;
+            int key0 = 8 * (r >> 2) + (r & 3), key1 = key0 + 4;
+            key0 = key0 < d.Nk2 ? key0 : d.Nk2 - 1;          // rows past Nk2: any valid row (their scores are masked)
+            key1 = key1 < d.Nk2 ? key1 : d.Nk2 - 1;
+            const frido_bf16* kp[2] = {k2b + (int64_t)key0 * d.ldk2, k2b + (int64_t)key1 * d.ldk2};
+            k2p[0] = kp[0];
+            k2p[1] = kp[1];
+#pragma unroll
+            for (int ks = 0; ks < K2E; ++ks) load_k2(ks);
         }
     }
     if (ln) {       // (uniform: every wave of the workgroup takes the two exchange barriers)
@@ -728,17 +770,170 @@ __global__ __launch_bounds__(512, 1) void flash_ds_kernel(const FridoAttnSmall d
         if (g == 0) xs[128 + wave * 16 + r] = hq;
         __syncthreads();
         const float rstd = 1.0f / sqrtf((xs[128 + (pair * 2) * 16 + r] + xs[128 + (pair * 2 + 1) * 16 + r]) * (1.0f / D) + d.ln_eps);
-        if (q_ok) {
+        if (!tail) {
+            if (q_ok) {
+#pragma unroll
+                for (int c = 0; c < CTH; ++c) {
+                    const int col = (hf * CTH + c) * 16 + g * 4;
+                    const float4 w = *reinterpret_cast<const float4*>(d.ln_w + col), bb = *reinterpret_cast<const float4*>(d.ln_b + col);
+                    const float y[4] = {(o[c][0] - mean) * rstd * w.x + bb.x, (o[c][1] - mean) * rstd * w.y + bb.y,
+                                        (o[c][2] - mean) * rstd * w.z + bb.z, (o[c][3] - mean) * rstd * w.w + bb.w};
+                    store_op4(d.ln_op, d.ln_lo, NS, grow * d.ld_ln + col, y);
+                    sat |= op_sat4(y);
+                }
+                status_raise(false, g == 0 && hf == 0 && stat_bad(mean, rstd));
+            }
+        } else if constexpr (G::TAIL) {
+            // ============ cross tail: h3 = softmax(alpha2 n2 K2^T) V2 + bias2 + h2 and its LayerNorm, on the rows still in registers ============
+            // (every lane runs it: the lanes of a ragged block's missing queries repeat the sample's last row and store nothing)
+            if (q_ok) status_raise(false, g == 0 && hf == 0 && stat_bad(mean, rstd));
+            // n2 as the hi / lo planes the stored operand would hold (split_op2: store_op4's bits), kept as B fragments: the lane's n2
+            // values of the fragment pair (c, c + 1) -- channels 16 c + 4 g + e and 16 (c + 1) + 4 g + e -- are declared the 8 k-slots
+            // 8 g .. 8 g + 7 of one 32-deep step; K2 is loaded in the same channel order below
+            uint32_t nh[CTH][2], nl[CTH][2];
 #pragma unroll
             for (int c = 0; c < CTH; ++c) {
                 const int col = (hf * CTH + c) * 16 + g * 4;
                 const float4 w = *reinterpret_cast<const float4*>(d.ln_w + col), bb = *reinterpret_cast<const float4*>(d.ln_b + col);
                 const float y[4] = {(o[c][0] - mean) * rstd * w.x + bb.x, (o[c][1] - mean) * rstd * w.y + bb.y,
                                     (o[c][2] - mean) * rstd * w.z + bb.z, (o[c][3] - mean) * rstd * w.w + bb.w};
-                store_op4(d.ln_op, d.ln_lo, NS, grow * d.ld_ln + col, y);
+                split_op2(y[0], y[1], NS, nh[c][0], nl[c][0]);
+                split_op2(y[2], y[3], NS, nh[c][1], nl[c][1]);
                 sat |= op_sat4(y);
+                if (q_ok && d.ln_op) {
+                    const int64_t no = grow * d.ld_ln + col;
+                    *reinterpret_cast<uint2*>(d.ln_op + no) = make_uint2(nh[c][0], nh[c][1]);
+                    *reinterpret_cast<uint2*>(d.ln_op + d.ln_lo + no) = make_uint2(nl[c][0], nl[c][1]);
+                }
             }
-            status_raise(false, g == 0 && hf == 0 && stat_bad(mean, rstd));
+            // ---- step 1: partial scores S2^T[key][q] = K2 . n2^T over this wave's half of d (K2 fragments: fetched above).  The lane's 8
+            //      scores are keys 8 g .. 8 g + 7: the k-slots of the P2 operand.
+            f32x4 t0 = f32x4{0.f, 0.f, 0.f, 0.f}, t1 = t0;
+            {
+                __builtin_amdgcn_sched_barrier(0);      // (not above the n2 loop, whose parameters fill the registers)
+#pragma unroll
+                for (int ks = K2E; ks < CTH / 2; ++ks) load_k2(ks);
+#pragma unroll
+                for (int c = 0; c < CTH; c += 2) {
+                    const bf16x8(&ka)[2][NS] = k2f[c / 2];
+                    const bf16x8 bh = __builtin_bit_cast(bf16x8, u32x4{nh[c][0], nh[c][1], nh[c + 1][0], nh[c + 1][1]});
+                    const bf16x8 bl = __builtin_bit_cast(bf16x8, u32x4{nl[c][0], nl[c][1], nl[c + 1][0], nl[c + 1][1]});
+                    // (attn_small_kernel's term order: Q lo x K hi, Q hi x K lo, hi x hi)
+                    t0 = mfma_op<NS>(ka[0][0], bl, t0);
+                    t1 = mfma_op<NS>(ka[1][0], bl, t1);
+                    t0 = mfma_op<NS>(ka[0][1], bh, t0);
+                    t1 = mfma_op<NS>(ka[1][1], bh, t1);
+                    t0 = mfma_op<NS>(ka[0][0], bh, t0);
+                    t1 = mfma_op<NS>(ka[1][0], bh, t1);
+                }
+            }
+            // the pair's halves meet in LDS.  No DMA is in flight any more, so these are plain C++ accesses (the compiler covers the
+            // MFMA -> LDS wait states); the K ring is free since the barrier above: every wave has left the main loop.
+            //   bytes 0 .. 16 Ki: partial scores (8 floats per lane); then 256 floats for the two LayerNorm exchanges
+            f32x4* xt = reinterpret_cast<f32x4*>(smem);
+            float* xs2 = reinterpret_cast<float*>(smem + G::XCH);
+            __builtin_amdgcn_sched_barrier(0);      // (not above the MFMAs that free the K2 / n2 registers)
+            // (the V2^T fragments of step 3 go out in front of the exchange barrier: their round trip runs under it and the softmax)
+            bf16x8 v2f[CTH][NS];
+            {
+                const frido_bf16* v2b = d.VT2 + (int64_t)z * d.vt2_bs + (int64_t)(hf * (D / 2) + r) * d.ldvt2 + g * 8;
+#pragma unroll
+                for (int c = 0; c < CTH; ++c) {
+                    const frido_bf16* src = v2b + (int64_t)c * 16 * d.ldvt2;
+                    v2f[c][0] = *reinterpret_cast<const bf16x8*>(src);
+                    v2f[c][1] = *reinterpret_cast<const bf16x8*>(src + d.vt2_lo);
+                }
+            }
+            xt[(wave * 64 + lane) * 2] = t0;
+            xt[(wave * 64 + lane) * 2 + 1] = t1;
+            __syncthreads();
+            const f32x4 u0 = xt[((wave ^ 1) * 64 + lane) * 2], u1 = xt[((wave ^ 1) * 64 + lane) * 2 + 1];
+            // ---- step 2: softmax over the Nk2 <= 32 keys (mine + partner's: a + b == b + a, identical bits in both waves) ----
+            const float a2 = d.alpha2;
+            float sv[8] = {(t0[0] + u0[0]) * a2, (t0[1] + u0[1]) * a2, (t0[2] + u0[2]) * a2, (t0[3] + u0[3]) * a2,
+                           (t1[0] + u1[0]) * a2, (t1[1] + u1[1]) * a2, (t1[2] + u1[2]) * a2, (t1[3] + u1[3]) * a2};
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                if (8 * g + i >= d.Nk2) sv[i] = -1.0e30f;
+            float mx = fmaxf(fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3])), fmaxf(fmaxf(sv[4], sv[5]), fmaxf(sv[6], sv[7])));
+            mx = xor_max(mx);
+            float pv[8], rs = 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                pv[i] = __expf(sv[i] - mx);
+                rs += pv[i];
+            }
+            const float inv2 = 1.0f / xor_sum(rs);
+            if (q_ok) status_raise(false, g == 0 && hf == 0 && stat_bad(mx, inv2));
+            bf16x8 pf[NS];
+            {
+                uint32_t h[4], l[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) split_op2(pv[2 * i] * inv2, pv[2 * i + 1] * inv2, NS, h[i], l[i]);
+                pf[0] = __builtin_bit_cast(bf16x8, u32x4{h[0], h[1], h[2], h[3]});
+                pf[1] = __builtin_bit_cast(bf16x8, u32x4{l[0], l[1], l[2], l[3]});
+            }
+            // ---- step 3: O2^T[this half] = V2^T P2^T (one 32-key step), + bias2 + h2 ----
+            float lsum2 = 0.f;
+#pragma unroll
+            for (int c = 0; c < CTH; ++c) {
+                f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+                acc = mfma_op<NS>(v2f[c][0], pf[1], acc);      // (attn_small_kernel's term order: P lo x V hi, P hi x V lo, hi x hi)
+                acc = mfma_op<NS>(v2f[c][1], pf[0], acc);
+                acc = mfma_op<NS>(v2f[c][0], pf[0], acc);
+                if (d.bias2) {
+                    const float4 bb = *reinterpret_cast<const float4*>(d.bias2 + (hf * CTH + c) * 16 + g * 4);
+                    acc[0] += bb.x; acc[1] += bb.y; acc[2] += bb.z; acc[3] += bb.w;
+                }
+                o[c] = f32x4{acc[0] + o[c][0], acc[1] + o[c][1], acc[2] + o[c][2], acc[3] + o[c][3]};
+                lsum2 += (o[c][0] + o[c][1]) + (o[c][2] + o[c][3]);
+            }
+            // ---- step 4: h3 out, and its two-pass LayerNorm (the exchange above, at its own LDS words: no barrier in front).  The
+            //      weights go out in front of its two barriers ----
+            __builtin_amdgcn_sched_barrier(0);      // (not above the MFMAs that free the V2^T registers)
+            float4 w2f[CTH];
+            if (d.ln2_op) {
+#pragma unroll
+                for (int c = 0; c < CTH; ++c) w2f[c] = *reinterpret_cast<const float4*>(d.ln2_w + (hf * CTH + c) * 16 + g * 4);
+            }
+            const float hs2 = xor_sum(lsum2);
+            if (g == 0) xs2[wave * 16 + r] = hs2;
+            if (q_ok && (d.out2_op || d.out2_act)) {
+#pragma unroll
+                for (int c = 0; c < CTH; ++c) {
+                    const int col = (hf * CTH + c) * 16 + g * 4;
+                    const float vv[4] = {o[c][0], o[c][1], o[c][2], o[c][3]};
+                    if (d.out2_act) *reinterpret_cast<float4*>(d.out2_act + grow * d.ld_act2 + col) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+                    if (d.out2_op) {
+                        store_op4(d.out2_op, d.out2_lo, NS, grow * d.ldo2 + col, vv);
+                        sat |= op_sat4(vv);
+                    }
+                }
+            }
+            __syncthreads();
+            const float mean2 = (xs2[(pair * 2) * 16 + r] + xs2[(pair * 2 + 1) * 16 + r]) * (1.0f / D);
+            float q2 = 0.f;
+#pragma unroll
+            for (int c = 0; c < CTH; ++c) {
+                const float a0 = o[c][0] - mean2, a1 = o[c][1] - mean2, a2c = o[c][2] - mean2, a3 = o[c][3] - mean2;
+                q2 += (a0 * a0 + a1 * a1) + (a2c * a2c + a3 * a3);
+            }
+            const float hq2 = xor_sum(q2);
+            if (g == 0) xs2[128 + wave * 16 + r] = hq2;
+            __syncthreads();
+            const float rstd2 = 1.0f / sqrtf((xs2[128 + (pair * 2) * 16 + r] + xs2[128 + (pair * 2 + 1) * 16 + r]) * (1.0f / D) + d.ln2_eps);
+            if (q_ok && d.ln2_op) {
+#pragma unroll
+                for (int c = 0; c < CTH; ++c) {
+                    const int col = (hf * CTH + c) * 16 + g * 4;
+                    const float4 w = w2f[c], bb = *reinterpret_cast<const float4*>(d.ln2_b + col);
+                    const float y[4] = {(o[c][0] - mean2) * rstd2 * w.x + bb.x, (o[c][1] - mean2) * rstd2 * w.y + bb.y,
+                                        (o[c][2] - mean2) * rstd2 * w.z + bb.z, (o[c][3] - mean2) * rstd2 * w.w + bb.w};
+                    store_op4(d.ln2_op, d.ln2_lo, NS, grow * d.ld_ln2 + col, y);
+                    sat |= op_sat4(y);
+                }
+                status_raise(false, g == 0 && hf == 0 && stat_bad(mean2, rstd2));
+            }
         }
     }
     status_raise(sat);
@@ -809,8 +1004,23 @@ extern "C" int frido_attn_flash_supported(int32_t dd) { return dd == 128 || dd =
 extern "C" int frido_attn_flash_ln_supported(int32_t dd) { return dd == 256 || dd == 384 || dd == 512; }
 
 extern "C" int frido_attn_flash(const FridoAttnSmall* d, frido_stream_t s) {
-    FRIDO_REQUIRE(d && d->Q && d->K && d->VT && (d->out_op || d->out_act), "null pointer");
-    FRIDO_REQUIRE(!d->out_act || ((d->ld_act & 3) == 0 && (d->ldr & 3) == 0), "stream strides must be multiples of 4");
+    FRIDO_REQUIRE(d && d->Q && d->K && d->VT && (d->out_op || d->out_act || d->K2), "null pointer");
+    // ---- the cross tail (FridoAttnSmall.K2 ...): absent = all zero; present = the d-split kernel's row-owning stream form ----
+    const bool tail = d->K2 != nullptr;
+    FRIDO_REQUIRE(tail || (!d->VT2 && !d->Nk2 && !d->bias2 && !d->ln2_w && !d->ln2_b && !d->ln2_op && !d->out2_op && !d->out2_act),
+                  "cross tail: fields set without K2 (an absent tail is all zero)");
+    FRIDO_REQUIRE(!tail || (d->nsplit == 2 && (d->d == 256 || d->d == 384)),
+                  "cross tail: two-plane mode and a head width of the row-owning d-split kernel that carries it (256, 384)");
+    FRIDO_REQUIRE(!tail || (!d->out_op && !d->act_bf16 && d->residual), "cross tail: the f32 stream form with a residual (out_op unset; out_act may be null = not stored)");
+    FRIDO_REQUIRE(!tail || (d->ln_w && d->ln_b && (!d->ln2_op || (d->ln2_w && d->ln2_b))), "cross tail: LayerNorm weight and bias given (ln_w, ln_b; ln2_w, ln2_b with ln2_op)");
+    FRIDO_REQUIRE(!tail || (d->VT2 && d->Nk2 >= 1 && d->Nk2 <= 32 && d->ldvt2 >= 32), "cross tail: 1 <= Nk2 <= 32, V2^T rows zero-padded to 32 keys");
+    FRIDO_REQUIRE(!tail || ((d->ldk2 & 7) == 0 && (d->k2_lo & 7) == 0 && (d->k2_bs & 7) == 0 && (d->ldvt2 & 7) == 0 && (d->vt2_lo & 7) == 0 && (d->vt2_bs & 7) == 0 &&
+                            (d->ldo2 & 3) == 0 && (d->out2_lo & 3) == 0 && (d->ld_ln2 & 3) == 0 && (d->ln2_lo & 3) == 0 && (d->ld_act2 & 3) == 0 &&
+                            (d->ld_ln & 3) == 0 && (d->ln_lo & 3) == 0 && aligned16(d->K2) && aligned16(d->VT2) && aligned16(d->bias2) && aligned16(d->ln2_w) &&
+                            aligned16(d->ln2_b) && aligned16(d->out2_act)),
+                  "cross tail: strides, plane offsets and pointers must keep 16-byte alignment");
+    FRIDO_REQUIRE(!tail || d->out2_op || d->out2_act || d->ln2_op, "cross tail: at least one of out2_op, out2_act, ln2_op");
+    FRIDO_REQUIRE(!(d->out_act || tail) || ((d->ld_act & 3) == 0 && (d->ldr & 3) == 0), "stream strides must be multiples of 4");
     FRIDO_REQUIRE(d->B > 0 && d->Nq > 0 && d->Nk > 0, "empty problem");
     FRIDO_REQUIRE(d->d == d->dv && frido_attn_flash_supported(d->d), "d = dv must be one of 128, 256, 384, 512, 576");
     FRIDO_REQUIRE(d->ldvt >= ((d->Nk + 31) & ~31) && (d->ldvt & 7) == 0, "V^T rows must be zero-padded to a multiple of 32 keys");
@@ -819,7 +1029,7 @@ extern "C" int frido_attn_flash(const FridoAttnSmall* d, frido_stream_t s) {
                   "strides and plane offsets must keep 16-byte alignment");
     FRIDO_REQUIRE(d->nsplit == 1 || d->nsplit == 2, "nsplit must be 1 or 2");
     FRIDO_REQUIRE(!d->skip_act_store, "skip_act_store is served by frido_attn_small only");
-    FRIDO_REQUIRE(!d->ln_op || (d->out_act && !d->act_bf16 && d->nsplit == 2 && frido_attn_flash_ln_supported(d->d) && d->ln_w && d->ln_b && (d->ld_ln & 3) == 0 &&
+    FRIDO_REQUIRE(!d->ln_op || ((d->out_act || tail) && !d->act_bf16 && d->nsplit == 2 && frido_attn_flash_ln_supported(d->d) && d->ln_w && d->ln_b && (d->ld_ln & 3) == 0 &&
                                 (d->ln_lo & 3) == 0),
                   "ln_op: bf16x3 f32-stream output with a head width whose workgroup owns whole rows (frido_attn_flash_ln_supported), weight and bias given");
     hipStream_t st = (hipStream_t)s;

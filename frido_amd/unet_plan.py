@@ -308,22 +308,31 @@ class UNetStagePlan:
         with b.gemm_pair():      # two projections of the same rows, independent of each other
             b.v_transposed(n1, C, wvo, Bx, HW, C, out=vT)
             qp = b.linear(n1, None, wop=wq, bias=False, out="op")
-        h2 = b.attention(qp, C, n1, C, vT, Bx, HW, HW, C, bias_ptr=bvo, residual=hcur, stream=True, ln=(t + ".norm2", 1e-5))
-        qp.free()
-        n1.free()
-        hcur.free()
-        # --- cross-attention (K, V^T cached per sample)
-        n2 = getattr(h2, "ln_copy", None)       # (r03) the attention kernel's epilogue may have produced it
-        if n2 is None:
-            n2 = b.layernorm(h2, t + ".norm2")
         kc, vTc, bvo2 = self.kv[(pre, dpt)]     # kc = ctx (W_q^T W_k)^T: the query projection is folded into the cached keys
         chain = last and C % 64 == 0       # proj_out(h3 + ff2(gg)) + x in ONE GEMM (needs h3 as an operand along K)
-        # (r05) with FF2 + proj_out chained, h3 is read only as an operand (A2 of that GEMM) and through norm3: where the kernel
-        # produces both copies itself the f32 rows are not stored at all
-        h3 = b.attention(n2, C, kc, C, vTc, Bx, HW, self.nctx, C, bias_ptr=bvo2, residual=h2, stream=True, also_op=chain,
-                         ln=(t + ".norm3", 1e-5), stream_dead=chain)
-        n2.free()
-        h2.free()
+        if b.attention_chain_ok(C, C, HW, C, self.nctx, C):
+            # the 32 x 32 plane: the flash launch owns whole rows of h2 / n2 and runs the 26-key cross-attention and norm3 on them
+            # itself -- one launch, and neither tensor makes the round trip through HBM (csrc/flash.hip, the cross tail)
+            h3 = b.attention_chain(qp, C, n1, C, vT, Bx, HW, HW, C, bias_ptr=bvo, residual=hcur, ln=(t + ".norm2", 1e-5), k2=kc, ldk2=C,
+                                   vT2=vTc, Nk2=self.nctx, bias2_ptr=bvo2, ln2=(t + ".norm3", 1e-5), also_op=chain, stream_dead=chain)
+            qp.free()
+            n1.free()
+            hcur.free()
+        else:
+            h2 = b.attention(qp, C, n1, C, vT, Bx, HW, HW, C, bias_ptr=bvo, residual=hcur, stream=True, ln=(t + ".norm2", 1e-5))
+            qp.free()
+            n1.free()
+            hcur.free()
+            # --- cross-attention (K, V^T cached per sample)
+            n2 = getattr(h2, "ln_copy", None)       # (r03) the attention kernel's epilogue may have produced it
+            if n2 is None:
+                n2 = b.layernorm(h2, t + ".norm2")
+            # (r05) with FF2 + proj_out chained, h3 is read only as an operand (A2 of that GEMM) and through norm3: where the kernel
+            # produces both copies itself the f32 rows are not stored at all
+            h3 = b.attention(n2, C, kc, C, vTc, Bx, HW, self.nctx, C, bias_ptr=bvo2, residual=h2, stream=True, also_op=chain,
+                             ln=(t + ".norm3", 1e-5), stream_dead=chain)
+            n2.free()
+            h2.free()
         # --- GEGLU feed-forward (attention.py:37-64)
         n3 = getattr(h3, "ln_copy", None)
         if n3 is None:

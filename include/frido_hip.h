@@ -267,6 +267,25 @@ typedef struct FridoAttnSmall {
        (O + bias + residual), whose values leave only as the operand copy (out_op) and / or the fused LayerNorm (ln_op).  The
        transformer block's h3 = attn2(norm2(h2)) + h2 (attention.py:226) is read by nothing else once FF2 + proj_out are one GEMM. */
     int32_t skip_act_store;
+    /* optional CROSS TAIL (frido_attn_flash only, two-plane mode, d = 256 or 384: the d-split kernel's workgroups own whole rows and
+       have the registers; everything else is rejected by name).  Present when K2 is non-null; every field is zero otherwise.  The
+       launch then also runs the short-key attention that follows a self-attention in a transformer block
+       (attention.py:225-226) on the rows it still holds in registers:
+           h2 = softmax(alpha Q K^T) V + bias + residual        (out_act may be NULL: not stored)
+           n2 = LayerNorm(h2; ln_w, ln_b, ln_eps)               (ln_op may be NULL: not stored; ln_w / ln_b stay required)
+           h3 = softmax(alpha2 n2 K2^T) V2 + bias2 + h2         n2 enters the product as the hi / lo planes ln_op would hold
+           out2_op  <- h3 as hi / lo operand planes (ldo2)      optional
+           out2_act <- h3 as f32 rows (ld_act2)                 optional
+           ln2_op   <- LayerNorm(h3; ln2_w, ln2_b, ln2_eps)     optional, hi / lo planes (ld_ln2)
+       K2 rows [B][Nk2] of d channels (per-sample stride k2_bs, row stride ldk2), VT2 = V2 transposed [B][d][ldvt2] with zero columns
+       beyond Nk2, 1 <= Nk2 <= 32 <= ldvt2.  At least one of out2_op / out2_act / ln2_op must be given. */
+    const frido_bf16* K2; int64_t k2_lo; int64_t k2_bs; int32_t ldk2;
+    const frido_bf16* VT2; int64_t vt2_lo; int64_t vt2_bs; int32_t ldvt2;
+    int32_t Nk2; float alpha2; const float* bias2;
+    const float* ln2_w; const float* ln2_b; float ln2_eps;
+    frido_bf16* ln2_op; int64_t ln2_lo; int32_t ld_ln2;
+    frido_bf16* out2_op; int64_t out2_lo; int32_t ldo2;
+    float* out2_act; int32_t ld_act2;
 } FridoAttnSmall;
 
 /* Multi-head flash attention for SMALL head dimensions (d = 32 or 64; frido_attn_mh_supported): per sample b and head h

@@ -26,7 +26,7 @@ def walk(prog, name, sp):
             if names[kind] == "GEMM":
                 desc = f"M={st.M} N={st.N} K={st.K}+{st.K2} conv={st.conv} tile={st.tile} geglu={st.geglu} out_op={bool(st.out_op)} out_f32={bool(st.out_f32)} gn={bool(st.gn_x1)} raw={bool(st.raw_x1)} sk={st.splitk}"
             elif names[kind] in ("ATTN_SMALL", "ATTN_FLASH"):
-                desc = f"B={st.B} Nq={st.Nq} Nk={st.Nk} d={st.d} out_op={bool(st.out_op)} ln={bool(st.ln_op)} skip={st.skip_act_store}"
+                desc = f"B={st.B} Nq={st.Nq} Nk={st.Nk} d={st.d} out_op={bool(st.out_op)} ln={bool(st.ln_op)} skip={st.skip_act_store}" + (f" +cross Nk2={st.Nk2}" if st.K2 else "")
             elif names[kind] == "ATTN_MH":
                 desc = f"B={st.B} heads={st.heads} Nq={st.Nq} Nk={st.Nk} d={st.d}"
             elif names[kind] in ("GN_FUSED", "GN_APPLY", "GN_STATS"):

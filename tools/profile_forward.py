@@ -39,6 +39,9 @@ def table(prog, sp, title, top=None):
         if n in ("ATTN_SMALL", "ATTN_FLASH"):
             desc = f"B={st.B} Nq={st.Nq} Nk={st.Nk} d={st.d}"
             fl = 4.0 * st.B * st.Nq * st.Nk * st.d
+            if st.K2:      # the cross tail: the block's short-key attention and norm3 ride in this launch
+                n, desc = "ATTN_FLASH+CROSS", desc + f" Nk2={st.Nk2}"
+                fl += 4.0 * st.B * st.Nq * st.Nk2 * st.d
         if n == "ATTN_MH":
             desc = f"B={st.B} heads={st.heads} Nq={st.Nq} Nk={st.Nk} d={st.d}"
             fl = 4.0 * st.B * st.heads * st.Nq * st.Nk * st.d
