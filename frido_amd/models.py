@@ -617,6 +617,23 @@ class FrozenCLIPTextEmbedder(_TextTower):
         return z.expand(-1, self.n_repeat, -1).contiguous()      # repeat(z, 'b 1 d -> b k d', k=n_repeat)
 
 
+def _captured(plan, sp):
+    """plan.launch(sp) -- kernels beside programs -- as one hipGraph captured on the stream `sp` (frido_capture_begin / frido_capture_end)."""
+    import ctypes
+    from .engine import Graph
+    L = _lib.lib()
+    _lib.check(L.frido_capture_begin(sp), "frido_capture_begin")
+    h = ctypes.c_void_p()
+    try:
+        plan.launch(sp)
+    except Exception:
+        if L.frido_capture_end(sp, ctypes.byref(h)) == 0:      # a failed body still has to end its capture
+            L.frido_graph_destroy(h)
+        raise
+    _lib.check(L.frido_capture_end(sp, ctypes.byref(h)), "frido_capture_end")
+    return Graph(h, plan)
+
+
 class FrozenClipImageEmbedder(_Versioned, nn.Module):
     """The third embedder of frido/modules/encoders/modules.py (:222-254): the image tower of OpenAI CLIP.  `forward` takes images
     [B, 3, H, W] float32 in [-1, 1] on the GPU and returns `encode_image`'s [B, embed_dim] float32, NOT normalised, like the reference:
@@ -704,19 +721,7 @@ class FrozenClipImageEmbedder(_Versioned, nn.Module):
 
     def _capture(self, plan, sp):
         """plan.graph: the preprocess launch and the tower's program as one hipGraph, captured on the stream `sp`."""
-        import ctypes
-        from .engine import Graph
-        L = _lib.lib()
-        _lib.check(L.frido_capture_begin(sp), "frido_capture_begin")
-        h = ctypes.c_void_p()
-        try:
-            plan.launch(sp)
-        except Exception:
-            if L.frido_capture_end(sp, ctypes.byref(h)) == 0:      # a failed body still has to end its capture
-                L.frido_graph_destroy(h)
-            raise
-        _lib.check(L.frido_capture_end(sp, ctypes.byref(h)), "frido_capture_end")
-        plan.graph = Graph(h, plan)
+        plan.graph = _captured(plan, sp)
         self.graph_captures += 1
 
     graph_captures = 0      # graphs captured so far (one per input shape in the cache; tests read it)
@@ -741,6 +746,203 @@ class FrozenClipImageEmbedder(_Versioned, nn.Module):
                 self._capture(plan, sp)
             plan.graph.launch(sp)
             return plan.out.clone()
+
+
+# ---- perceptual metric (taming/modules/losses/lpips.py:11-122) -----------------------------------------
+class _LinWeight(nn.Module):      # nn.Conv2d(chn_in, 1, 1, bias=False)
+    def __init__(self, chn_in):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(1, chn_in, 1, 1))
+
+
+class _Scaling(nn.Module):        # ScalingLayer, lpips.py:57-64: persistent buffers, they are keys of the reference's state_dict
+    def __init__(self):
+        super().__init__()
+        from .lpips import SCALE, SHIFT
+        self.register_buffer("shift", torch.Tensor(SHIFT)[None, :, None, None])
+        self.register_buffer("scale", torch.Tensor(SCALE)[None, :, None, None])
+
+
+class LPIPS(_Versioned, nn.Module):
+    """taming/modules/losses/lpips.py:11-54, the learned perceptual metric: a frozen VGG16 feature stack, a per-pixel channel
+    normalisation and five 1 x 1 projections.  `forward(input, target)` takes two [B, 3, H, W] float32 image batches on the GPU and
+    returns the reference's [B, 1, 1, 1] float32; `per_layer` returns the five spatial means it adds, [B, 5].  Input and target go
+    through the tower together as ONE batch of 2B (frido_amd/lpips.py LpipsPlan); the four kernels of csrc/lpips.hip and the five slice
+    programs replay as ONE captured graph per input shape (B, H, W), the plans kept least-recently-used.
+
+    Parameters carry the reference's names -- net.sliceK.N.{weight,bias}, linK.model.1.weight (index 0 under use_dropout=False), the
+    buffers scaling_layer.{shift,scale} -- so the `loss.perceptual_loss.*` keys of a taming checkpoint load.  Dropout is the eval-mode
+    identity and every parameter is frozen.  The constructor downloads NOTHING: `lin_ckpt=` loads a local vgg.pth (strict=False),
+    `vgg_ckpt=` a local torchvision vgg16 state_dict (features.N.* -> the slice names); without either the weights are this module's
+    own init (He-normal convs, zero biases, uniform [0, 1) projections), which measures nothing perceptual.
+    Refused by name: from_pretrained / load_from_pretrained without a local path, .train() under use_dropout=True, inputs that are not
+    two equal [B, 3, H, W] shapes with H, W >= 16 (four floor-mode pools), CPU tensors."""
+
+    _what = "LPIPS"
+
+    def __init__(self, use_dropout=True, *, lin_ckpt=None, vgg_ckpt=None, precision=None):
+        super().__init__()
+        from .lpips import CHNS, VGG_SLICES
+        self.use_dropout, self.precision = bool(use_dropout), precision
+        self.chns = list(CHNS)
+        self.scaling_layer = _Scaling()
+        self.net = holders.Nop()
+        cin = 3
+        for si, convs in enumerate(VGG_SLICES):
+            sl = nn.Sequential()
+            for idx, cout in convs:
+                sl.add_module(str(idx), holders.Conv(cin, cout, 3))
+                cin = cout
+            setattr(self.net, f"slice{si + 1}", sl)
+        self.net.N_slices = 5
+        for k, c in enumerate(self.chns):
+            lin = holders.Nop()
+            lin.model = nn.Sequential()
+            lin.model.add_module(str(self._lin_index), _LinWeight(c))
+            setattr(self, f"lin{k}", lin)
+        with torch.no_grad():
+            for name, p in self.named_parameters():
+                if name.startswith("lin"):
+                    p.uniform_(0.0, 1.0)
+                elif name.endswith(".bias"):
+                    p.zero_()
+                else:
+                    nn.init.kaiming_normal_(p, nonlinearity="relu")
+        self._init_versioning()
+        if vgg_ckpt is not None:
+            self.load_vgg16(vgg_ckpt)
+        if lin_ckpt is not None:
+            self.load_from_pretrained(path=lin_ckpt)
+        for p in self.parameters():
+            p.requires_grad = False
+        super().train(False)
+
+    _lin_index = property(lambda self: 1 if self.use_dropout else 0)
+
+    def _init_versioning(self):
+        super()._init_versioning()
+        self._plans = {}
+
+    def invalidate(self):
+        self._rt = None
+        self._plans = {}
+
+    def lin_names(self):
+        return [f"lin{k}.model.{self._lin_index}.weight" for k in range(5)]
+
+    def train(self, mode=True):
+        if mode and self.use_dropout:
+            raise NotImplementedError("LPIPS.train(): use_dropout=True puts nn.Dropout in front of every 1 x 1 projection (lpips.py:71), and "
+                                      "training-mode dropout is not built: the metric is the eval-mode identity (keep .eval(), or build "
+                                      "LPIPS(use_dropout=False))")
+        return super().train(mode)
+
+    # ---- weights: local files only ----------------------------------------------------------------------
+    def load_from_pretrained(self, name="vgg_lpips", path=None):
+        """lpips.py:27-30 with the download taken out: `path` is a local vgg.pth (the linK.model.1.weight keys)."""
+        if path is None:
+            raise NotImplementedError(f"LPIPS.load_from_pretrained('{name}'): the reference downloads vgg.pth (taming.util.get_ckpt_path, "
+                                      "heibox.uni-heidelberg.de) -- nothing is downloaded here; pass path= / lin_ckpt= a local copy")
+        sd = torch.load(path, map_location=torch.device("cpu"))
+        fixed = {}
+        for k, v in sd.items():      # a checkpoint written under the other use_dropout has the projections one index away
+            parts = k.split(".")
+            if len(parts) == 4 and parts[0][:3] == "lin" and parts[1] == "model" and parts[2] in ("0", "1"):
+                parts[2] = str(self._lin_index)
+            fixed[".".join(parts)] = v
+        return self.load_state_dict(fixed, strict=False)
+
+    @classmethod
+    def from_pretrained(cls, name="vgg_lpips", path=None, **kw):
+        """lpips.py:32-39 with the download taken out."""
+        if name != "vgg_lpips":
+            raise NotImplementedError(f"LPIPS.from_pretrained('{name}'): only 'vgg_lpips' exists (lpips.py:34-35)")
+        if path is None:
+            raise NotImplementedError("LPIPS.from_pretrained('vgg_lpips'): the reference downloads vgg.pth and torchvision's vgg16 weights "
+                                      "-- nothing is downloaded here; pass path= a local vgg.pth (and vgg_ckpt= a local vgg16 state_dict)")
+        return cls(lin_ckpt=path, **kw)
+
+    def load_vgg16(self, path):
+        """A local torchvision vgg16 state_dict: features.N.{weight,bias} -> net.sliceK.N.{weight,bias}; the classifier's keys are
+        passed over."""
+        from .lpips import VGG_SLICES
+        sd = torch.load(path, map_location=torch.device("cpu"))
+        mapped = {}
+        for si, convs in enumerate(VGG_SLICES):
+            for idx, _ in convs:
+                for leaf in ("weight", "bias"):
+                    src = f"features.{idx}.{leaf}"
+                    if src not in sd:
+                        raise KeyError(f"LPIPS.load_vgg16: {path} holds no '{src}' (not a torchvision vgg16 state_dict?)")
+                    mapped[f"net.slice{si + 1}.{idx}.{leaf}"] = sd[src]
+        return self.load_state_dict(mapped, strict=False)
+
+    # ---- the metric ----------------------------------------------------------------------------------------
+    def _check(self, x, y):
+        from .lpips import MIN_SIDE
+        for name, t in (("input", x), ("target", y)):
+            if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != 3 or 0 in t.shape:
+                got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+                raise ValueError(f"LPIPS: {name} must be a [B, 3, H, W] tensor, got {got}")
+        if x.shape != y.shape:
+            raise ValueError(f"LPIPS: input {tuple(x.shape)} and target {tuple(y.shape)} differ in shape")
+        if min(x.shape[2:]) < MIN_SIDE:
+            raise ValueError(f"LPIPS: H and W must be at least {MIN_SIDE} (VGG16's four 2 x 2 pools leave nothing of a {x.shape[2]} x "
+                             f"{x.shape[3]} image)")
+        _on_gpu(self._what, self, x, y)
+
+    def _make_plan(self, B, H, W):
+        from .lpips import LpipsPlan
+        shift = [float(v) for v in self.scaling_layer.shift.flatten().tolist()]
+        scale = [float(v) for v in self.scaling_layer.scale.flatten().tolist()]
+        return LpipsPlan(self._rt, B=B, H=H, W=W, shift=shift, scale=scale, lin_names=self.lin_names())
+
+    def _capture(self, plan, sp):
+        """plan.graph: the plan's launches as one hipGraph, captured on the stream `sp`.  A shape the conv launcher turns away is a
+        ValueError naming it."""
+        try:
+            plan.graph = _captured(plan, sp)
+        except FridoHipError as e:
+            B, _, H, W = plan.x_in.shape
+            raise ValueError(f"LPIPS: the library refuses a launch of the (B, H, W) = ({B}, {H}, {W}) plan: {e}") from e
+        self.graph_captures += 1
+
+    graph_captures = 0      # graphs captured so far (one per input shape in the cache; tests read it)
+
+    @torch.no_grad()
+    @_lib.with_planes
+    def _run(self, x, y):
+        """The plan of the inputs' shape after its graph ran on them."""
+        self._check(x, y)
+        dev = next(self.parameters()).device
+        B, _, H, W = x.shape
+        with own_stream(self, dev) as sp:
+            if self._rt is None:
+                self._plans = {}
+                self._rt = runtime.module_builder(self, dev, self.precision)
+
+            def build():      # like _cached_plan; an evicted plan's graph may still be running on this stream: wait for it first
+                with self._rt.persist_scope() as owned:
+                    return self._make_plan(B, H, W), owned
+            plan = lru_entry(self._plans, (B, H, W), PLAN_CACHE_SIZE, build, before_evict=self._stream.synchronize)[0]
+            plan.x_in.copy_(x)
+            plan.y_in.copy_(y)
+            if plan.graph is None:
+                try:
+                    self._capture(plan, sp)
+                except ValueError:
+                    self._plans.pop((B, H, W), None)
+                    raise
+            plan.graph.launch(sp)
+            return plan
+
+    def forward(self, input, target):
+        """lpips.py:41-54: [B, 1, 1, 1] float32."""
+        return self._run(input, target).out.clone().view(-1, 1, 1, 1)
+
+    def per_layer(self, input, target):
+        """The five spatial means forward adds (lpips.py:50), [B, 5] float32, relu1_2 first."""
+        return self._run(input, target).per_layer.clone()
 
 
 def _first(cond, n):

@@ -195,3 +195,40 @@ def clip_score(image_embedder, text_embedder, images, text):
     if zt.shape != zi.shape:
         raise ValueError(f"clip_score: {zi.shape[0]} images but {zt.shape[0]} captions")
     return (zi * zt).sum(dim=-1)
+
+
+@torch.no_grad()
+def reconstruction_metrics(first_stage, images, lpips, *, perceptual_weight=1.0):
+    """What a tokenizer is judged by, per sample: a dict of [B] float32 tensors on the device for images [B, 3, H, W] in [-1, 1] on the GPU.
+        l1         mean |x - xrec|
+        mse, psnr  on [-1, 1], peak 2: psnr = 10 log10(4 / mse) (inf for an exact reconstruction)
+        lpips      lpips(x, xrec), a frido_amd.models.LPIPS
+        quant_loss the codebook loss `diff` of MSFPNVQModel.forward: ONE number for the batch (a mean over it, like the reference's),
+                   repeated per sample; absent for a VQModelInterface
+        nll_loss   l1 + perceptual_weight * lpips; its batch mean is taming/modules/losses/vqperceptual.py:85-100's nll_loss for
+                   xrec_aux=None (mean over the batch of |x - xrec| + w * p_loss, p_loss broadcast over the pixels)
+    first_stage: an MSFPNVQModel (its forward's `dec` and `diff`) or a VQModelInterface (encode -> decode).  The reconstruction and the
+    perceptual distance run on the HIP engine; the per-sample means are torch reductions of the two images.  The discriminator terms of
+    VQLPIPSWithDiscriminator (g_loss, d_weight) are not built.  With the weights of LPIPS's own init the `lpips` entry measures nothing
+    perceptual: load vgg.pth and a vgg16 state_dict for the published metric.
+    Under torch.distributed every rank scores its own shard; gathering the scores is the caller's."""
+    from .models import LPIPS, MSFPNVQModel, VQModelInterface
+    if not isinstance(lpips, LPIPS):
+        raise ValueError(f"reconstruction_metrics: lpips must be a frido_amd.models.LPIPS, got {type(lpips).__name__}")
+    if isinstance(first_stage, MSFPNVQModel):
+        out = first_stage(images)
+        xrec, diff = out[0], out[-2]          # (dec, diff, info), or (dec, aux, diff, info) under use_aux_loss
+    elif isinstance(first_stage, VQModelInterface):
+        xrec, diff = first_stage.decode(first_stage.encode(images)), None
+    else:
+        raise ValueError(f"reconstruction_metrics: first_stage must be an MSFPNVQModel or a VQModelInterface, got {type(first_stage).__name__}")
+    x = images.float()
+    xrec = xrec.float()
+    err = x - xrec
+    l1 = err.abs().mean(dim=(1, 2, 3))
+    mse = (err * err).mean(dim=(1, 2, 3))
+    lp = lpips(x.contiguous(), xrec.contiguous()).view(-1)
+    res = dict(l1=l1, mse=mse, psnr=10.0 * torch.log10(4.0 / mse), lpips=lp, nll_loss=l1 + float(perceptual_weight) * lp)
+    if diff is not None:
+        res["quant_loss"] = diff.float().reshape(1).expand(x.shape[0]).clone()
+    return res

@@ -55,6 +55,17 @@ def _fill_heavy(name, shape, rng, leaf):
     return (0.5 * rng.standard_normal(shape)).astype(np.float32)
 
 
+def _fill_lpips(name, shape, rng, leaf):
+    """Third filler: the LPIPS module (frido_amd.models.LPIPS / taming's own, same names).  Thirteen conv + ReLU layers in a row with no
+    normalisation between them need He scale to keep the features O(1) down to relu5_3 -- std = sqrt(2 / fan_in), fan_in = 9 Cin --
+    with small biases, 0.05 N(0, 1); the 1 x 1 projections linK.model.N.weight are non-negative like the trained ones, uniform in [0, 1)."""
+    if any(part[:3] == "lin" and part[3:].isdigit() for part in name.split(".")):
+        return rng.uniform(0.0, 1.0, shape).astype(np.float32)
+    if leaf == "weight":
+        return (rng.standard_normal(shape) * np.sqrt(2.0 / int(np.prod(shape[1:])))).astype(np.float32)
+    return (0.05 * rng.standard_normal(shape)).astype(np.float32)
+
+
 _CACHE = None      # {(name, shape, profile): array} when enable_cache() was called (the GPU suite: tests/conftest.py)
 
 
@@ -68,7 +79,7 @@ def enable_cache():
 
 def fill_tensor(name, shape, profile=None):
     """float32 array for parameter `name` (a state_dict key) of `shape`.  profile None: the fan-in-scaled N(0, sigma) filler every
-    fixture of rounds 1-4 uses; "heavy": the trained-checkpoint-like dynamic range of _fill_heavy."""
+    fixture of rounds 1-4 uses; "heavy": the trained-checkpoint-like dynamic range of _fill_heavy; "lpips": _fill_lpips, for the LPIPS module only."""
     shape = tuple(int(s) for s in shape)
     if _CACHE is not None:
         key = (name, shape, profile)
@@ -86,6 +97,8 @@ def _fill_tensor(name, shape, profile):
         return np.asarray(1.0, dtype=np.float32)
     if profile == "heavy":
         return _fill_heavy(name, shape, rng, leaf)
+    if profile == "lpips":
+        return _fill_lpips(name, shape, rng, leaf)
     if profile is not None:
         raise ValueError(f"unknown filler profile {profile!r}")
     if "embedding.weight" in name or name.endswith("emb.weight") or "stage_emb" in name:
