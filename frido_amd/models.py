@@ -232,7 +232,7 @@ class _FirstStage(_Versioned, _Base):
         self.encoder.multiscale = edconfig["multiscale"]
         self.encoder.resolution = edconfig["resolution"]
         # lossconfig: VQLPIPSWithDiscriminator is LPIPS (VGG weights: a download) + a PatchGAN trained by the backward pass -- whatever
-        # the target, the module holds the no-op loss
+        # the target, the module holds the no-op loss (MSFPNVQModel's with_loss=True replaces it afterwards)
         self.loss = DummyLoss()
         nres = len(edconfig["ch_mult"])
         self.res_list = [edconfig["resolution"] / 2 ** (nres - i - 1) for i in range(edconfig["multiscale"])]
@@ -293,13 +293,16 @@ class MSFPNVQModel(_FirstStage):
 
     CHANNEL ORDER: `quant` is [fine .. coarse] (the reference reverses its list before the concat, msvqgan.py:146), coarser scales
     nearest-upsampled to the finest grid -- the OPPOSITE of VQModelInterface.encode's [coarse .. fine].
-    Same parameter / state_dict key set as the reference's class; no backward pass, no LPIPS / PatchGAN loss module."""
+    Same parameter / state_dict key set as the reference's class; no backward pass.  The loss module is the no-op DummyLoss unless the
+    model is built with `with_loss=True`: then `lossconfig` is instantiated (VQLPIPSWithDiscriminator: LPIPS + the PatchGAN
+    discriminator, forward-only) and `validation_step` evaluates it."""
 
     _what = "MSFPNVQModel"
 
     def __init__(self, edconfig, ddconfig, lossconfig, n_embed, embed_dim, fusion="concat", ckpt_path=None, ignore_keys=[],
                  image_key="image", colorize_nlabels=None, monitor=None, remap=None, sane_index_shape=False, on_vit=[],
-                 use_aux_loss=False, unsample_type="nearest", quant_beta=0.25, legacy=True, init_normal=False, precision=None):
+                 use_aux_loss=False, unsample_type="nearest", quant_beta=0.25, legacy=True, init_normal=False, precision=None, *,
+                 with_loss=False):
         if remap is not None:
             raise NotImplementedError("remap: the quantiser's index remapping (quantize.py:229-241) is not built; no shipped config sets it")
         if fusion != "concat":
@@ -315,6 +318,18 @@ class MSFPNVQModel(_FirstStage):
             q.legacy, q.sane_index_shape = legacy, sane_index_shape
         self.use_aux_loss, self.unsample_type = use_aux_loss, unsample_type
         self.sane_index_shape, self.quant_beta, self.legacy = sane_index_shape, quant_beta, legacy
+        if with_loss:
+            # opt-in: the lossconfig is instantiated (a DummyLoss target stays the no-op); the state_dict then carries the reference's
+            # `loss.perceptual_loss.*` / `loss.discriminator.*` keys.  The checkpoint, if any, is read again so that they load.
+            lossconfig = _plain(lossconfig)
+            if not str(lossconfig.get("target", "")).endswith("DummyLoss"):
+                if precision is not None:      # the loss's two networks run on the build the tokenizer runs on
+                    lossconfig = dict(lossconfig, params=dict(lossconfig.get("params") or {}, precision=precision))
+                self.loss = instantiate_from_config(lossconfig)
+                if ckpt_path is not None:
+                    self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
+
+    global_step = 0      # what a trainer counts; validation_step hands it to the loss (disc_factor is 0 before disc_start)
 
     def _check_image(self, x, what):
         if x.shape[1] > 3:
@@ -389,9 +404,25 @@ class MSFPNVQModel(_FirstStage):
     def configure_optimizers(self):
         raise FridoHipError("configure_optimizers: no backward pass exists on the HIP path, so there is nothing to optimise")
 
+    @torch.no_grad()
     def validation_step(self, batch, batch_idx):
-        raise NotImplementedError("validation_step: its loss module is LPIPS + a PatchGAN discriminator (VQLPIPSWithDiscriminator), whose weights "
-                                  "are a download / come from training; the part of the objective that exists here is the codebook loss, encode()[1]")
+        """msvqgan.py:223-242 with a VQLPIPSWithDiscriminator in `self.loss` (with_loss=True, or assigned): forward, the loss for both
+        optimizer indices from one evaluation, `self.log` / `self.log_dict`.  Returns the merged dict of the two logs (the reference
+        returns the bound method `self.log_dict`)."""
+        if isinstance(self.loss, DummyLoss):
+            raise NotImplementedError("validation_step: its loss module is LPIPS + a PatchGAN discriminator (VQLPIPSWithDiscriminator), whose weights "
+                                      "are a download / come from training; the part of the objective that exists here is the codebook loss, encode()[1]")
+        if self.use_aux_loss:
+            raise NotImplementedError("validation_step: use_aux_loss=True hands the loss xrec_aux, whose term the reference's own "
+                                      "vqperceptual.py:96 cannot evaluate (an in-place add of a [B, 3, H, W] tensor into a [1] tensor)")
+        x = self.get_input(batch, self.image_key).to(self.device)
+        xrec, qloss, _ = self(x)
+        (aeloss, log_dict_ae), (discloss, log_dict_disc) = self.loss.evaluate(qloss, x, xrec, self.global_step, split="val")
+        self.log("val/rec_loss", log_dict_ae["val/rec_loss"], prog_bar=True, logger=True, on_step=True, on_epoch=True, sync_dist=True)
+        self.log("val/aeloss", aeloss, prog_bar=True, logger=True, on_step=True, on_epoch=True, sync_dist=True)
+        self.log_dict(log_dict_ae)
+        self.log_dict(log_dict_disc)
+        return {**log_dict_ae, **log_dict_disc}
 
     def test_step(self, batch, batch_idx):
         """msvqgan.py:244-245."""
@@ -943,6 +974,293 @@ class LPIPS(_Versioned, nn.Module):
     def per_layer(self, input, target):
         """The five spatial means forward adds (lpips.py:50), [B, 5] float32, relu1_2 first."""
         return self._run(input, target).per_layer.clone()
+
+
+# ---- PatchGAN discriminator and the tokenizer's loss (taming/modules/discriminator/model.py, losses/vqperceptual.py) ------------------
+def weights_init(m):
+    """discriminator/model.py:8-14."""
+    classname = m.__class__.__name__
+    if classname.find("Conv") != -1:
+        nn.init.normal_(m.weight.data, 0.0, 0.02)
+    elif classname.find("BatchNorm") != -1:
+        nn.init.normal_(m.weight.data, 1.0, 0.02)
+        nn.init.constant_(m.bias.data, 0)
+
+
+class ActNorm(nn.Module):
+    """taming/modules/util.py:10-20 as a parameter holder: loc, scale [1, C, 1, 1] and the `initialized` flag.  Its data-dependent
+    initialisation runs in training mode only, which the discriminator refuses; the forward h = scale (x + loc) is folded into the
+    discriminator's affine kernel (frido_amd/patchgan.py fold_actnorm)."""
+
+    def __init__(self, num_features, logdet=False, affine=True, allow_reverse_init=False):
+        assert affine
+        super().__init__()
+        self.logdet, self.allow_reverse_init = logdet, allow_reverse_init
+        self.loc = nn.Parameter(torch.zeros(1, num_features, 1, 1))
+        self.scale = nn.Parameter(torch.ones(1, num_features, 1, 1))
+        self.register_buffer("initialized", torch.tensor(0, dtype=torch.uint8))
+
+    def forward(self, input, reverse=False):
+        raise FridoHipError("ActNorm is a parameter holder here: NLayerDiscriminator folds it into its affine kernel")
+
+
+class NLayerDiscriminator(_Versioned, nn.Module):
+    """taming/modules/discriminator/model.py:17-67, the PatchGAN discriminator, forward-only: `forward(x)` takes [B, input_nc, H, W]
+    float32 images on the GPU and returns the [B, 1, Ho, Wo] float32 logits.  `pair(real, fake)` runs both batches through the net as ONE
+    batch of 2B and returns the plan with the logits and the GAN terms (frido_amd/patchgan.py PatchGanPlan).  The stem, the folded norms,
+    the head and the reductions are the kernels of csrc/patchgan.hip, the middle 4 x 4 convs run on the implicit GEMM; everything
+    replays as ONE captured graph per input shape, the plans kept least-recently-used.
+
+    `main` holds nn.Conv2d / nn.BatchNorm2d / ActNorm as PARAMETER HOLDERS under the reference's indices, so the state_dict is the
+    reference's (`loss.discriminator.*` of a taming checkpoint loads) and `weights_init` applies.  The norms are the eval-mode ones:
+    BatchNorm2d by its running statistics, ActNorm by its loc / scale.
+    Refused by name: .train() (batch statistics, ActNorm's data-dependent init), input_nc > 8, ndf % 4 != 0 or ndf * input_nc > 512 (the
+    stem kernel), n_layers < 1, an input too small for a 1 x 1 logit map, CPU tensors."""
+
+    _what = "NLayerDiscriminator"
+
+    def __init__(self, input_nc=3, ndf=64, n_layers=3, use_actnorm=False, *, precision=None):
+        super().__init__()
+        from . import patchgan as pg
+        if n_layers < 1:
+            raise ValueError(f"NLayerDiscriminator: n_layers={n_layers}: at least one stride-2 layer (the stem) is needed")
+        if input_nc > pg.MAX_INPUT_NC:
+            raise NotImplementedError(f"NLayerDiscriminator: input_nc={input_nc} > {pg.MAX_INPUT_NC}: the stem kernel (frido_disc_stem) takes at "
+                                      "most 8 input channels")
+        if ndf % 4 or ndf < 4:
+            raise NotImplementedError(f"NLayerDiscriminator: ndf={ndf} must be a multiple of 4 (16-byte stores across the channels)")
+        if ndf * input_nc > pg.STEM_MAX_WEIGHTS:
+            raise NotImplementedError(f"NLayerDiscriminator: ndf * input_nc = {ndf * input_nc} > {pg.STEM_MAX_WEIGHTS}: the stem's weights "
+                                      "must fit 32 KB of LDS")
+        self.input_nc, self.ndf, self.n_layers, self.use_actnorm, self.precision = input_nc, ndf, n_layers, bool(use_actnorm), precision
+        self.table = pg.layer_table(input_nc, ndf, n_layers)
+        self.main = nn.Sequential()
+        for ci, ni, cin, cout, stride in self.table:
+            self.main.add_module(str(ci), nn.Conv2d(cin, cout, kernel_size=pg.KW, stride=stride, padding=pg.PADW,
+                                                    bias=ni is None or self.use_actnorm))
+            if ni is not None:
+                self.main.add_module(str(ni), ActNorm(cout) if self.use_actnorm else nn.BatchNorm2d(cout))
+        self._init_versioning()
+        for p in self.parameters():
+            p.requires_grad = False
+        super().train(False)
+
+    def _init_versioning(self):
+        super()._init_versioning()
+        self._plans = {}
+        self._consts = None
+
+    def invalidate(self):
+        self._rt = None
+        self._plans = {}
+        self._consts = None
+
+    def _apply(self, fn, *a, **k):
+        self._plans, self._consts = {}, None
+        return super()._apply(fn, *a, **k)
+
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError("NLayerDiscriminator.train(): training mode means BatchNorm2d's batch statistics / ActNorm's "
+                                      "data-dependent initialisation and a backward pass, none of which is built: the net is the "
+                                      "eval-mode forward (keep .eval())")
+        return super().train(mode)
+
+    def apply(self, fn):      # nn.Module.apply; afterwards the compiled plans are stale
+        out = super().apply(fn)
+        self.invalidate()
+        return out
+
+    # ---- the forward -------------------------------------------------------------------------------------
+    def _check(self, *images):
+        from . import patchgan as pg
+        for t in images:
+            if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != self.input_nc or 0 in t.shape:
+                got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+                raise ValueError(f"NLayerDiscriminator: images must be a [B, {self.input_nc}, H, W] tensor, got {got}")
+        if len(images) == 2 and images[0].shape != images[1].shape:
+            raise ValueError(f"NLayerDiscriminator: real {tuple(images[0].shape)} and fake {tuple(images[1].shape)} differ in shape")
+        H, W = images[0].shape[2:]
+        if pg.plane_sizes(H, W, self.n_layers) is None:
+            raise ValueError(f"NLayerDiscriminator: a {H} x {W} input is too small for a 1 x 1 logit map after {self.n_layers} stride-2 "
+                             f"and two stride-1 4 x 4 convs (the smallest side is {self.min_side()})")
+        _on_gpu(self._what, self, *images)
+
+    def min_side(self):
+        from . import patchgan as pg
+        h = 1
+        while pg.plane_sizes(h, h, self.n_layers) is None:
+            h += 1
+        return h
+
+    def _make_consts(self, b):
+        """What the side launches read, made once per Builder: the repacked stem / head weights and the folded norms, on the device."""
+        from . import patchgan as pg
+        sd = {k: v.detach().cpu() for k, v in self.state_dict().items()}
+        last = self.table[-1][0]
+        affine = {}
+        for ci, ni, _, _, _ in self.table:
+            if ni is not None:
+                a, bb = pg.fold_norm(sd, "", ci, ni, self.use_actnorm)
+                affine[ni] = (b.to_dev(a), b.to_dev(bb))
+        return dict(stem_w=b.to_dev(pg.repack_stem_weight(sd["main.0.weight"])), stem_b=b.to_dev(sd["main.0.bias"]),
+                    head_w=b.to_dev(pg.repack_head_weight(sd[f"main.{last}.weight"])), head_b=float(sd[f"main.{last}.bias"].float()[0]),
+                    affine=affine)
+
+    def _capture(self, plan, sp):
+        try:
+            plan.graph = _captured(plan, sp)
+        except FridoHipError as e:
+            raise ValueError(f"NLayerDiscriminator: the library refuses a launch of the {tuple(plan.x_in.shape)} plan: {e}") from e
+        self.graph_captures += 1
+
+    graph_captures = 0      # graphs captured so far (one per input shape in the cache; tests read it)
+
+    @torch.no_grad()
+    @_lib.with_planes
+    def _run(self, x, y=None):
+        """The plan of the inputs' shape after its graph ran on them (y: the fake images of a pair, or None)."""
+        from .patchgan import PatchGanPlan
+        self._check(*((x,) if y is None else (x, y)))
+        dev = next(self.parameters()).device
+        B, _, H, W = x.shape
+        pair = y is not None
+        with own_stream(self, dev) as sp:
+            if self._rt is None:
+                self._plans, self._consts = {}, None
+                self._rt = runtime.module_builder(self, dev, self.precision)
+            if self._consts is None:
+                self._consts = self._make_consts(self._rt)
+
+            def build():      # like _cached_plan; an evicted plan's graph may still be running on this stream: wait for it first
+                with self._rt.persist_scope() as owned:
+                    return PatchGanPlan(self._rt, B=B, H=H, W=W, pair=pair, input_nc=self.input_nc, ndf=self.ndf, n_layers=self.n_layers,
+                                        consts=self._consts), owned
+            key = (B, H, W, pair)
+            plan = lru_entry(self._plans, key, PLAN_CACHE_SIZE, build, before_evict=self._stream.synchronize)[0]
+            plan.x_in.copy_(x)
+            if pair:
+                plan.y_in.copy_(y)
+            if plan.graph is None:
+                try:
+                    self._capture(plan, sp)
+                except ValueError:
+                    self._plans.pop(key, None)
+                    raise
+            plan.graph.launch(sp)
+            return plan
+
+    def forward(self, input):
+        """model.py:65-67: [B, 1, Ho, Wo] float32 logits."""
+        return self._run(input).logits.clone()
+
+    def pair(self, real, fake):
+        """Both batches through the net at once: the plan, whose `logits` [2B, 1, Ho, Wo] (real first), `out` [5]
+        (patchgan.OUT_NAMES) and `per_sample` [2B] logit means are valid until its next run."""
+        return self._run(real, fake)
+
+
+def adopt_weight(weight, global_step, threshold=0, value=0.):
+    """vqperceptual.py:16-19."""
+    if global_step < threshold:
+        weight = value
+    return weight
+
+
+def hinge_d_loss(logits_real, logits_fake):
+    """vqperceptual.py:22-26, in torch: for callers that hold logits; VQLPIPSWithDiscriminator takes the value from its graph."""
+    return 0.5 * (torch.mean(torch.relu(1. - logits_real)) + torch.mean(torch.relu(1. + logits_fake)))
+
+
+def vanilla_d_loss(logits_real, logits_fake):
+    """vqperceptual.py:29-33, in torch."""
+    return 0.5 * (torch.mean(nn.functional.softplus(-logits_real)) + torch.mean(nn.functional.softplus(logits_fake)))
+
+
+class VQLPIPSWithDiscriminator(nn.Module):
+    """taming/modules/losses/vqperceptual.py:36-150, the loss of every shipped tokenizer config, evaluated WITHOUT a gradient: under
+    no_grad the reference's calculate_adaptive_weight raises and d_weight is 0 (vqperceptual.py:113-117), so what is left is LPIPS, the
+    discriminator's forward on both images and a handful of reductions.  The children are named `perceptual_loss` (LPIPS) and
+    `discriminator` (NLayerDiscriminator): the `loss.*` keys of a taming checkpoint load.
+
+    `forward` returns the reference's (loss, log) for optimizer_idx 0 or 1 with exactly its keys; `evaluate` returns both pairs from one
+    launch of the discriminator's graph (real and fake as one batch of 2B) and one of LPIPS's.  |x - xrec| and the final scalar
+    combinations are torch reductions on the device.  `disc_factor` and `d_weight` entries are host tensors like the reference's.
+    Nothing is downloaded: LPIPS holds its own init until `perceptual_loss` is loaded from local files.
+    Refused by name: .train(), disc_conditional=True / cond=, xrec_aux (the reference's own line 96 adds a [B, 3, H, W] tensor in place
+    into a [1] tensor and raises), unequal input / reconstruction shapes, CPU tensors."""
+
+    def __init__(self, disc_start, codebook_weight=1.0, pixelloss_weight=1.0, disc_num_layers=3, disc_in_channels=3, disc_factor=1.0,
+                 disc_weight=1.0, perceptual_weight=1.0, use_actnorm=False, disc_conditional=False, disc_ndf=64, disc_loss="hinge",
+                 aux_downscale=4., aux_loss_weight=[1., 0], *, precision=None):
+        super().__init__()
+        assert disc_loss in ["hinge", "vanilla"]
+        if disc_conditional:
+            raise NotImplementedError("VQLPIPSWithDiscriminator: disc_conditional=True (the conditioning concatenated to the discriminator's "
+                                      "input, vqperceptual.py:108-110) is not built; no shipped config sets it")
+        self.codebook_weight, self.pixel_weight, self.perceptual_weight = codebook_weight, pixelloss_weight, perceptual_weight
+        self.aux_downscale, self.aux_loss_weight = aux_downscale, aux_loss_weight
+        self.perceptual_loss = LPIPS(precision=precision).eval()
+        self.discriminator = NLayerDiscriminator(input_nc=disc_in_channels, n_layers=disc_num_layers, use_actnorm=use_actnorm, ndf=disc_ndf,
+                                                 precision=precision).apply(weights_init)
+        self.discriminator_iter_start = disc_start
+        self.disc_loss_name = disc_loss
+        self.disc_loss = hinge_d_loss if disc_loss == "hinge" else vanilla_d_loss
+        self.disc_factor, self.discriminator_weight, self.disc_conditional = disc_factor, disc_weight, disc_conditional
+        super().train(False)
+
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError("VQLPIPSWithDiscriminator.train(): the loss is evaluated without a gradient (the reference asserts "
+                                      "`not self.training` on that path, vqperceptual.py:116); there is no backward pass, keep .eval()")
+        return super().train(mode)
+
+    @torch.no_grad()
+    def evaluate(self, codebook_loss, inputs, reconstructions, global_step, split="train"):
+        """((loss, log) of optimizer_idx 0, (d_loss, log) of optimizer_idx 1): vqperceptual.py:85-150 for cond=None, xrec_aux=None."""
+        from .patchgan import OUT_NAMES
+        for name, t in (("inputs", inputs), ("reconstructions", reconstructions)):
+            if not torch.is_tensor(t) or t.dim() != 4:
+                raise ValueError(f"VQLPIPSWithDiscriminator: {name} must be a [B, C, H, W] tensor")
+        if inputs.shape != reconstructions.shape:
+            raise ValueError(f"VQLPIPSWithDiscriminator: inputs {tuple(inputs.shape)} and reconstructions {tuple(reconstructions.shape)} "
+                             "differ in shape")
+        _on_gpu("VQLPIPSWithDiscriminator", self.discriminator, inputs, reconstructions)
+        x, xrec = inputs.contiguous().float(), reconstructions.contiguous().float()
+        rec_loss = torch.abs(x - xrec)
+        if self.perceptual_weight > 0:
+            p_loss = self.perceptual_loss(x, xrec)
+            rec_loss = rec_loss + self.perceptual_weight * p_loss
+        else:
+            p_loss = torch.tensor([0.0])
+        rec_aux_loss = torch.tensor([0.0])
+        nll_loss = torch.mean(rec_loss)
+        out = self.discriminator.pair(x, xrec).out.clone()
+        val = dict(zip(OUT_NAMES, out.unbind(0)))
+        g_loss = val["g_loss"]
+        d_weight = torch.tensor(0.0)          # no gradient: vqperceptual.py:115-117
+        disc_factor = adopt_weight(self.disc_factor, global_step, threshold=self.discriminator_iter_start)
+        cb = codebook_loss.detach().float().mean()
+        loss = nll_loss + d_weight * disc_factor * g_loss + self.codebook_weight * cb
+        log0 = {f"{split}/total_loss": loss.clone().detach().mean(), f"{split}/quant_loss": cb, f"{split}/nll_loss": nll_loss.detach().mean(),
+                f"{split}/rec_loss": rec_loss.detach().mean(), f"{split}/p_loss": p_loss.detach().mean(),
+                f"{split}/rec_aux_loss": rec_aux_loss.detach().mean(), f"{split}/d_weight": d_weight.detach(),
+                f"{split}/disc_factor": torch.tensor(disc_factor), f"{split}/g_loss": g_loss.detach().mean()}
+        d_loss = disc_factor * val["hinge" if self.disc_loss_name == "hinge" else "vanilla"]
+        log1 = {f"{split}/disc_loss": d_loss.clone().detach().mean(), f"{split}/logits_real": val["logits_real"].detach().mean(),
+                f"{split}/logits_fake": val["logits_fake"].detach().mean()}
+        return (loss, log0), (d_loss, log1)
+
+    def forward(self, codebook_loss, inputs, reconstructions, optimizer_idx, global_step, last_layer=None, cond=None, split="train",
+                xrec_aux=None):
+        if cond is not None:
+            raise NotImplementedError("VQLPIPSWithDiscriminator: cond= (a conditional discriminator, vqperceptual.py:108-110, 139-141) is not built")
+        if xrec_aux is not None:
+            raise NotImplementedError("VQLPIPSWithDiscriminator: xrec_aux= is not built: the reference's own line 96 adds a [B, 3, H, W] tensor "
+                                      "in place into a [1] tensor and raises")
+        if optimizer_idx not in (0, 1):
+            raise ValueError(f"VQLPIPSWithDiscriminator: optimizer_idx must be 0 or 1, got {optimizer_idx!r}")
+        return self.evaluate(codebook_loss, inputs, reconstructions, global_step, split)[optimizer_idx]
 
 
 def _first(cond, n):

@@ -198,7 +198,7 @@ def clip_score(image_embedder, text_embedder, images, text):
 
 
 @torch.no_grad()
-def reconstruction_metrics(first_stage, images, lpips, *, perceptual_weight=1.0):
+def reconstruction_metrics(first_stage, images, lpips, *, perceptual_weight=1.0, discriminator=None):
     """What a tokenizer is judged by, per sample: a dict of [B] float32 tensors on the device for images [B, 3, H, W] in [-1, 1] on the GPU.
         l1         mean |x - xrec|
         mse, psnr  on [-1, 1], peak 2: psnr = 10 log10(4 / mse) (inf for an exact reconstruction)
@@ -208,13 +208,19 @@ def reconstruction_metrics(first_stage, images, lpips, *, perceptual_weight=1.0)
         nll_loss   l1 + perceptual_weight * lpips; its batch mean is taming/modules/losses/vqperceptual.py:85-100's nll_loss for
                    xrec_aux=None (mean over the batch of |x - xrec| + w * p_loss, p_loss broadcast over the pixels)
     first_stage: an MSFPNVQModel (its forward's `dec` and `diff`) or a VQModelInterface (encode -> decode).  The reconstruction and the
-    perceptual distance run on the HIP engine; the per-sample means are torch reductions of the two images.  The discriminator terms of
-    VQLPIPSWithDiscriminator (g_loss, d_weight) are not built.  With the weights of LPIPS's own init the `lpips` entry measures nothing
+    perceptual distance run on the HIP engine; the per-sample means are torch reductions of the two images.
+    discriminator: an NLayerDiscriminator adds, per sample, the means of its logit maps,
+        logits_real  on the image,  logits_fake  on the reconstruction
+    from one run of both through the net (the batch means of vqperceptual.py:147-148 are their means; the whole loss with g_loss and
+    disc_loss is VQLPIPSWithDiscriminator.evaluate).  With filler or freshly initialised weights they say nothing about image quality.
+    With the weights of LPIPS's own init the `lpips` entry measures nothing
     perceptual: load vgg.pth and a vgg16 state_dict for the published metric.
     Under torch.distributed every rank scores its own shard; gathering the scores is the caller's."""
-    from .models import LPIPS, MSFPNVQModel, VQModelInterface
+    from .models import LPIPS, MSFPNVQModel, NLayerDiscriminator, VQModelInterface
     if not isinstance(lpips, LPIPS):
         raise ValueError(f"reconstruction_metrics: lpips must be a frido_amd.models.LPIPS, got {type(lpips).__name__}")
+    if discriminator is not None and not isinstance(discriminator, NLayerDiscriminator):
+        raise ValueError(f"reconstruction_metrics: discriminator must be a frido_amd.models.NLayerDiscriminator, got {type(discriminator).__name__}")
     if isinstance(first_stage, MSFPNVQModel):
         out = first_stage(images)
         xrec, diff = out[0], out[-2]          # (dec, diff, info), or (dec, aux, diff, info) under use_aux_loss
@@ -231,4 +237,7 @@ def reconstruction_metrics(first_stage, images, lpips, *, perceptual_weight=1.0)
     res = dict(l1=l1, mse=mse, psnr=10.0 * torch.log10(4.0 / mse), lpips=lp, nll_loss=l1 + float(perceptual_weight) * lp)
     if diff is not None:
         res["quant_loss"] = diff.float().reshape(1).expand(x.shape[0]).clone()
+    if discriminator is not None:
+        per = discriminator.pair(x.contiguous(), xrec.contiguous()).per_sample.clone()
+        res["logits_real"], res["logits_fake"] = per[:x.shape[0]], per[x.shape[0]:]
     return res

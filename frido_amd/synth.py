@@ -66,6 +66,23 @@ def _fill_lpips(name, shape, rng, leaf):
     return (0.05 * rng.standard_normal(shape)).astype(np.float32)
 
 
+PATCHGAN_GAIN = 2.0      # on He scale: the logits of a filled discriminator then spread over several units, both hinges clip
+
+
+def _fill_patchgan(name, shape, rng, leaf):
+    """Fourth filler: the PatchGAN discriminator (frido_amd.models.NLayerDiscriminator / taming's own, same state_dict names; buffers
+    too).  Conv weights PATCHGAN_GAIN x He scale so that a good share of the logits lies beyond +-1 (where relu(1 - l) and relu(1 + l)
+    clip: a swapped sign then shows); per-channel DISTINCT norm statistics: running_var in [0.5, 2), running_mean 0.3 N(0, 1), BatchNorm
+    weight in [0.5, 1.5), ActNorm scale in [0.5, 1.5) and loc 0.3 N(0, 1); biases 0.1 N(0, 1)."""
+    if leaf == "weight" and len(shape) == 4:
+        return (rng.standard_normal(shape) * PATCHGAN_GAIN * np.sqrt(2.0 / int(np.prod(shape[1:])))).astype(np.float32)
+    if leaf in ("running_var", "weight", "scale"):
+        return rng.uniform(0.5, 1.5 if leaf != "running_var" else 2.0, shape).astype(np.float32)
+    if leaf in ("running_mean", "loc"):
+        return (0.3 * rng.standard_normal(shape)).astype(np.float32)
+    return (0.1 * rng.standard_normal(shape)).astype(np.float32)
+
+
 _CACHE = None      # {(name, shape, profile): array} when enable_cache() was called (the GPU suite: tests/conftest.py)
 
 
@@ -79,7 +96,8 @@ def enable_cache():
 
 def fill_tensor(name, shape, profile=None):
     """float32 array for parameter `name` (a state_dict key) of `shape`.  profile None: the fan-in-scaled N(0, sigma) filler every
-    fixture of rounds 1-4 uses; "heavy": the trained-checkpoint-like dynamic range of _fill_heavy; "lpips": _fill_lpips, for the LPIPS module only."""
+    fixture of rounds 1-4 uses; "heavy": the trained-checkpoint-like dynamic range of _fill_heavy; "lpips": _fill_lpips, for the LPIPS module only;
+    "patchgan": _fill_patchgan, for the discriminator only."""
     shape = tuple(int(s) for s in shape)
     if _CACHE is not None:
         key = (name, shape, profile)
@@ -99,6 +117,8 @@ def _fill_tensor(name, shape, profile):
         return _fill_heavy(name, shape, rng, leaf)
     if profile == "lpips":
         return _fill_lpips(name, shape, rng, leaf)
+    if profile == "patchgan":
+        return _fill_patchgan(name, shape, rng, leaf)
     if profile is not None:
         raise ValueError(f"unknown filler profile {profile!r}")
     if "embedding.weight" in name or name.endswith("emb.weight") or "stage_emb" in name:

@@ -1,2 +1,3 @@
-"""`taming.modules.losses.DummyLoss` (lossconfig.target of every shipped first-stage config) and the LPIPS perceptual metric."""
-from frido_amd.models import DummyLoss, LPIPS  # noqa: F401
+"""`taming.modules.losses.DummyLoss` (lossconfig.target of every shipped first-stage config), the LPIPS perceptual metric and the
+tokenizer's full loss."""
+from frido_amd.models import DummyLoss, LPIPS, VQLPIPSWithDiscriminator  # noqa: F401
