@@ -293,10 +293,12 @@ class Builder:
         return res
 
     def conv(self, a, B, Hs, Ws, wname, *, stride=1, pad=1, up=0, dn=0, Ho=None, Wo=None, bias=True,
-             rowvec=None, act=ACT_NONE, residual=None, out="f32", alpha=1.0):
-        """3x3 / 1x1 convolution of the NHWC operand `a` ([B*Hs*Ws][Cin_pad]).
+             rowvec=None, act=ACT_NONE, residual=None, out="f32", alpha=1.0, padx=None):
+        """kh x kw convolution (kh * kw <= 32 taps) of the NHWC operand `a` ([B*Hs*Ws][Cin_pad]).
         up: nearest x2^up up-sampling folded in (pyunet.py:119); dn: source sampled at stride 2^dn
-        (spade_norm.py:52 nearest down-resize).  Returns F32 or POperand [B*Ho*Wo][Cout]."""
+        (spade_norm.py:52 nearest down-resize).  pad is the top padding and padx the left one, None = the same as pad (the geometry
+        then carries no padx of its own: Prog.gemm fills it in); the (1, 7) / (7, 1) kernels of Inception-v3 pass 0 / 3 and 3 / 0.
+        Returns F32 or POperand [B*Ho*Wo][Cout]."""
         wop, cp = self.conv_weight(wname + ".weight")
         w = self.w[wname + ".weight"]
         co, _, kh, kw = w.shape
@@ -304,10 +306,12 @@ class Builder:
         Hl, Wl = (Hs << up) >> dn, (Ws << up) >> dn
         if Ho is None:
             Ho = (Hl + 2 * pad - kh) // stride + 1
-            Wo = (Wl + 2 * pad - kw) // stride + 1
+            Wo = (Wl + 2 * (pad if padx is None else padx) - kw) // stride + 1
         M = B * Ho * Wo
         geom = dict(Hs=Hs, Ws=Ws, Cin=cp, Hl=Hl, Wl=Wl, Ho=Ho, Wo=Wo, kh=kh, kw=kw, stride=stride, pad=pad,
                     up_shift=up, dn_shift=dn)
+        if padx is not None:
+            geom["padx"] = padx
         return self._gemm_out(M, co, kh * kw * cp, a, wop, conv=geom, bias=self.bias(wname + ".bias") if bias else None,
                               rowvec=rowvec, act=act, residual=residual, out=out, alpha=alpha)
 

@@ -976,6 +976,140 @@ class LPIPS(_Versioned, nn.Module):
         return self._run(input, target).per_layer.clone()
 
 
+# ---- Inception-v3 feature extractor of the Fréchet Inception Distance ----------------------------------
+class _BasicConv(nn.Module):      # torchvision's BasicConv2d: the parameter holders only
+    def __init__(self, cin, cout, kh, kw, stride, pad, padx):
+        super().__init__()
+        from .fid import BN_EPS
+        self.conv = nn.Conv2d(cin, cout, (kh, kw), stride=stride, padding=(pad, padx), bias=False)
+        self.bn = nn.BatchNorm2d(cout, eps=BN_EPS)
+
+
+class FIDInceptionV3(_Versioned, nn.Module):
+    """The feature extractor of the Fréchet Inception Distance: torchvision's Inception-v3 in the FID variant torch-fidelity's
+    FeatureExtractorInceptionV3 runs (every average pool leaves the padding out of its divisor, Mixed_7c pools with a maximum), forward
+    only and always in eval mode.  `forward(images)` returns [B, 2048] float32, the pooled features that package calls '2048'.
+    `images`: uint8 [B, H, W, 3] on the GPU (what pipeline.sample_images gathers), or float32 [B, 3, H, W] in [-1, 1] (what the decoders
+    return), which is first quantised to 8 bits the way the sampling script writes images: `quant` = "pil" (custom_to_pil, the PNG
+    writer: the default, the evaluation reads PNG directories) or "np" (custom_to_np).  Then the TF1-legacy bilinear resize to
+    299 x 299 and (v - 128) / 128 (include/frido_fid.h), the 94 conv + BatchNorm + ReLU layers with the BatchNorm folded into the conv on
+    the host in float64, the pools and the global average (frido_amd/fid.py InceptionPlan; csrc/fid.hip), replayed as ONE captured
+    graph per input shape (B, H, W, dtype), the plans kept least-recently-used.
+
+    The parameter holders are nn.Conv2d(bias=False) and nn.BatchNorm2d(eps=1e-3) under torchvision's names (Conv2d_1a_3x3.conv.weight,
+    Mixed_5b.branch1x1.bn.running_var, ... and fc.weight / fc.bias, held but never run), so the published pt_inception-2015-12-05
+    state_dict loads: `ckpt=` is a LOCAL file, nothing is downloaded, a file without num_batches_tracked is accepted.  Without it the
+    weights are torch's initialisation and the features measure nothing about image quality.
+    `resolution=` (keyword only, fixed at construction) is the side the images are resized to: 299, the only value at which the features
+    are the published metric's; a smaller one runs the same tower on smaller planes.
+    Refused by name: .train() (NotImplementedError), inputs of neither layout / dtype or not 3 channels (ValueError), CPU tensors
+    (FridoHipError)."""
+
+    _what = "FIDInceptionV3"
+
+    def __init__(self, *, ckpt=None, precision=None, resolution=None):
+        super().__init__()
+        from . import fid
+        self.precision, self.quant = precision, "pil"
+        self.resolution = int(resolution or fid.RESOLUTION)
+        if fid.tower_planes(self.resolution) is None:
+            raise ValueError(f"FIDInceptionV3: a {self.resolution} x {self.resolution} tower input leaves some conv or pool without an "
+                             "output pixel")
+        for name, cin, cout, kh, kw, stride, pad, padx in fid.conv_table():
+            parent, parts = self, name.split(".")
+            for p in parts[:-1]:
+                if not hasattr(parent, p):
+                    setattr(parent, p, holders.Nop())
+                parent = getattr(parent, p)
+            setattr(parent, parts[-1], _BasicConv(cin, cout, kh, kw, stride, pad, padx))
+        self.fc = nn.Linear(fid.FC_SHAPE[1], fid.FC_SHAPE[0])
+        self._init_versioning()
+        if ckpt is not None:
+            self.load_checkpoint(ckpt)
+        for p in self.parameters():
+            p.requires_grad = False
+        super().train(False)
+
+    def _init_versioning(self):
+        super()._init_versioning()
+        self._plans = {}
+
+    def invalidate(self):
+        self._rt = None
+        self._plans = {}
+
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError("FIDInceptionV3.train(): the extractor is forward-only with its BatchNorm folded from the running "
+                                      "statistics; there is no training mode and no backward pass (keep .eval())")
+        return super().train(False)
+
+    def load_checkpoint(self, path):
+        """A local state_dict with this module's key set (pt_inception-2015-12-05).  The num_batches_tracked buffers may be missing;
+        anything else missing, and any key this module does not have, is a KeyError."""
+        sd = torch.load(path, map_location=torch.device("cpu"))
+        res = self.load_state_dict(sd, strict=False)
+        missing = [k for k in res.missing_keys if not k.endswith("num_batches_tracked")]
+        if missing or res.unexpected_keys:
+            raise KeyError(f"FIDInceptionV3.load_checkpoint: {path} is no Inception-v3 state_dict: missing {missing[:4]} "
+                           f"({len(missing)}), unexpected {list(res.unexpected_keys)[:4]} ({len(res.unexpected_keys)})")
+        return res
+
+    def _check(self, x, quant):
+        from .fid import QUANT
+        ok = torch.is_tensor(x) and x.dim() == 4 and 0 not in x.shape and (
+            (x.dtype == torch.uint8 and x.shape[3] == 3) or (x.dtype == torch.float32 and x.shape[1] == 3))
+        if not ok:
+            got = (tuple(x.shape), x.dtype) if torch.is_tensor(x) else type(x).__name__
+            raise ValueError("FIDInceptionV3: images must be uint8 [B, H, W, 3] or float32 [B, 3, H, W] in [-1, 1] with 3 channels, "
+                             f"got {got}")
+        if quant not in QUANT:
+            raise ValueError(f"FIDInceptionV3: quant must be one of {sorted(QUANT)}, got {quant!r}")
+        _on_gpu(self._what, self, x)
+
+    def _builder(self, dev):
+        """The Builder over the FOLDED weights (conv + BatchNorm as one conv with a bias), for the build `precision` selects."""
+        from . import fid
+        from .builder import Builder
+        planes = config.planes(self.precision)
+        with _lib.use_planes(planes):
+            dev = require_gpu(dev)
+        return Builder(dev, config.nsplit(self.precision), fid.folded_weights(self.state_dict(), dev), planes=planes)
+
+    def _capture(self, plan, sp):
+        """plan.graph: the plan's launches as one hipGraph, captured on the stream `sp`."""
+        plan.graph = _captured(plan, sp)
+        self.graph_captures += 1
+
+    graph_captures = 0      # graphs captured so far (one per input shape in the cache; tests read it)
+
+    @torch.no_grad()
+    @_lib.with_planes
+    def forward(self, images, quant=None):
+        from .fid import InceptionPlan
+        quant = quant or self.quant
+        self._check(images, quant)
+        S = self.resolution
+        dev = next(self.parameters()).device
+        uint8 = images.dtype == torch.uint8
+        B, H, W = (images.shape[0], images.shape[1], images.shape[2]) if uint8 else (images.shape[0], images.shape[2], images.shape[3])
+        key = (B, H, W, images.dtype, quant if not uint8 else None, S)
+        with own_stream(self, dev) as sp:
+            if self._rt is None:
+                self._plans = {}
+                self._rt = self._builder(dev)
+
+            def build():      # like _cached_plan; an evicted plan's graph may still be running on this stream: wait for it first
+                with self._rt.persist_scope() as owned:
+                    return InceptionPlan(self._rt, B=B, H=H, W=W, uint8=uint8, quant=quant, S=S), owned
+            plan = lru_entry(self._plans, key, PLAN_CACHE_SIZE, build, before_evict=self._stream.synchronize)[0]
+            plan.x_in.copy_(images)
+            if plan.graph is None:
+                self._capture(plan, sp)
+            plan.graph.launch(sp)
+            return plan.out.clone()
+
+
 # ---- PatchGAN discriminator and the tokenizer's loss (taming/modules/discriminator/model.py, losses/vqperceptual.py) ------------------
 def weights_init(m):
     """discriminator/model.py:8-14."""

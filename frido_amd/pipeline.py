@@ -241,3 +241,30 @@ def reconstruction_metrics(first_stage, images, lpips, *, perceptual_weight=1.0,
         per = discriminator.pair(x.contiguous(), xrec.contiguous()).per_sample.clone()
         res["logits_real"], res["logits_fake"] = per[:x.shape[0]], per[x.shape[0]:]
     return res
+
+
+@torch.no_grad()
+def fid_statistics(extractor, images, stats=None):
+    """The running feature statistics of a Fréchet Inception Distance after `images` were added: extractor(images) -> [B, 2048] float32
+    on the device, then one launch that adds sum x and sum x x^T in float64 (frido_amd.fid.FeatureStatistics.update).
+    extractor: a frido_amd.models.FIDInceptionV3; images: uint8 [B, H, W, 3] (what sample_images gathers) or float32 [B, 3, H, W] in
+    [-1, 1] (what the decoders return) on the GPU; stats: the statistics so far, None starts new ones.  Returns the updated statistics.
+    Under torch.distributed every rank adds its own shard; FeatureStatistics.all_gather_merge joins them in rank order."""
+    from .fid import FEATURES, FeatureStatistics
+    from .models import FIDInceptionV3
+    if not isinstance(extractor, FIDInceptionV3):
+        raise ValueError(f"fid_statistics: extractor must be a frido_amd.models.FIDInceptionV3, got {type(extractor).__name__}")
+    if stats is not None and not isinstance(stats, FeatureStatistics):
+        raise ValueError(f"fid_statistics: stats must be a frido_amd.fid.FeatureStatistics or None, got {type(stats).__name__}")
+    feats = extractor(images)
+    if stats is None:
+        stats = FeatureStatistics(FEATURES, feats.device)
+    return stats.update(feats)
+
+
+def fid(stats_a, stats_b):
+    """The Fréchet distance between the Gaussians of two FeatureStatistics, a float (frido_amd.fid.frechet_distance: float64, on the
+    host, once per evaluation).  With the published Inception weights loaded and enough samples on both sides this is FID; no trained
+    weights ship with this repository, and with anything else in the extractor the number measures nothing about image quality."""
+    from .fid import frechet_distance
+    return frechet_distance(stats_a.mean(), stats_a.cov(), stats_b.mean(), stats_b.cov())

@@ -83,6 +83,26 @@ def _fill_patchgan(name, shape, rng, leaf):
     return (0.1 * rng.standard_normal(shape)).astype(np.float32)
 
 
+INCEPTION_GAIN = 1.0     # on He scale; with the BatchNorm ranges below the 94 post-ReLU outputs stay O(1) from the stem to Mixed_7c
+
+
+def _fill_inception(name, shape, rng, leaf):
+    """Fifth filler: the Inception-v3 of the Fréchet distance (frido_amd.models.FIDInceptionV3, torchvision's names; buffers too).  94
+    conv + BatchNorm + ReLU layers: conv weights INCEPTION_GAIN x He scale, sqrt(2 / fan_in), so that a layer hands on the second
+    moment it received; per-channel DISTINCT BatchNorm statistics whose ratio gamma^2 / var averages about 1: running_var in
+    [0.5, 1.5) (positive), weight in [0.75, 1.25), running_mean and bias 0.1 N(0, 1) -- about half of every output survives its ReLU
+    and no output dies or saturates on the way down (tests/test_fid_host.py asserts it).  fc, never run, gets fan-in scale."""
+    if leaf == "weight" and len(shape) == 4:
+        return (rng.standard_normal(shape) * INCEPTION_GAIN * np.sqrt(2.0 / int(np.prod(shape[1:])))).astype(np.float32)
+    if leaf == "weight" and len(shape) == 2:
+        return (rng.standard_normal(shape) / np.sqrt(shape[1])).astype(np.float32)
+    if leaf == "running_var":
+        return rng.uniform(0.5, 1.5, shape).astype(np.float32)
+    if leaf == "weight":
+        return rng.uniform(0.75, 1.25, shape).astype(np.float32)
+    return (0.1 * rng.standard_normal(shape)).astype(np.float32)
+
+
 _CACHE = None      # {(name, shape, profile): array} when enable_cache() was called (the GPU suite: tests/conftest.py)
 
 
@@ -97,7 +117,7 @@ def enable_cache():
 def fill_tensor(name, shape, profile=None):
     """float32 array for parameter `name` (a state_dict key) of `shape`.  profile None: the fan-in-scaled N(0, sigma) filler every
     fixture of rounds 1-4 uses; "heavy": the trained-checkpoint-like dynamic range of _fill_heavy; "lpips": _fill_lpips, for the LPIPS module only;
-    "patchgan": _fill_patchgan, for the discriminator only."""
+    "patchgan": _fill_patchgan, for the discriminator only; "inception": _fill_inception, for FIDInceptionV3 only."""
     shape = tuple(int(s) for s in shape)
     if _CACHE is not None:
         key = (name, shape, profile)
@@ -119,6 +139,8 @@ def _fill_tensor(name, shape, profile):
         return _fill_lpips(name, shape, rng, leaf)
     if profile == "patchgan":
         return _fill_patchgan(name, shape, rng, leaf)
+    if profile == "inception":
+        return _fill_inception(name, shape, rng, leaf)
     if profile is not None:
         raise ValueError(f"unknown filler profile {profile!r}")
     if "embedding.weight" in name or name.endswith("emb.weight") or "stage_emb" in name:
