@@ -38,7 +38,7 @@ POOL_MAX_S2, POOL_MAX_S1P1, POOL_AVG_S1P1 = 0, 1, 2  # FRIDO_POOL3_*
 RESOLUTION = 299
 FEATURES = 2048
 BN_EPS = 1e-3                                        # BasicConv2d's BatchNorm2d(eps=0.001)
-FC_SHAPE = (1008, 2048)                              # held so that the published checkpoint loads, never run
+FC_SHAPE = (1008, 2048)                              # the checkpoint's fc: FIDInceptionV3.logits runs its weight (no bias), forward never
 MIN_SIDE = 1                                         # the resize takes any source size
 
 _bound = {}      # plane format -> {launcher name: function of that build}

@@ -988,7 +988,9 @@ class _BasicConv(nn.Module):      # torchvision's BasicConv2d: the parameter hol
 class FIDInceptionV3(_Versioned, nn.Module):
     """The feature extractor of the Fréchet Inception Distance: torchvision's Inception-v3 in the FID variant torch-fidelity's
     FeatureExtractorInceptionV3 runs (every average pool leaves the padding out of its divisor, Mixed_7c pools with a maximum), forward
-    only and always in eval mode.  `forward(images)` returns [B, 2048] float32, the pooled features that package calls '2048'.
+    only and always in eval mode.  `forward(images)` returns [B, 2048] float32, the pooled features that package calls '2048';
+    `logits(features)` maps them to [B, 1008] float32, features @ fc.weight.T WITHOUT the bias: that package's 'logits_unbiased', the
+    input of its Inception Score (frido_amd/fidelity.py).
     `images`: uint8 [B, H, W, 3] on the GPU (what pipeline.sample_images gathers), or float32 [B, 3, H, W] in [-1, 1] (what the decoders
     return), which is first quantised to 8 bits the way the sampling script writes images: `quant` = "pil" (custom_to_pil, the PNG
     writer: the default, the evaluation reads PNG directories) or "np" (custom_to_np).  Then the TF1-legacy bilinear resize to
@@ -997,7 +999,7 @@ class FIDInceptionV3(_Versioned, nn.Module):
     graph per input shape (B, H, W, dtype), the plans kept least-recently-used.
 
     The parameter holders are nn.Conv2d(bias=False) and nn.BatchNorm2d(eps=1e-3) under torchvision's names (Conv2d_1a_3x3.conv.weight,
-    Mixed_5b.branch1x1.bn.running_var, ... and fc.weight / fc.bias, held but never run), so the published pt_inception-2015-12-05
+    Mixed_5b.branch1x1.bn.running_var, ... and fc.weight / fc.bias: forward runs neither, logits the weight alone), so the published pt_inception-2015-12-05
     state_dict loads: `ckpt=` is a LOCAL file, nothing is downloaded, a file without num_batches_tracked is accepted.  Without it the
     weights are torch's initialisation and the features measure nothing about image quality.
     `resolution=` (keyword only, fixed at construction) is the side the images are resized to: 299, the only value at which the features
@@ -1108,6 +1110,17 @@ class FIDInceptionV3(_Versioned, nn.Module):
                 self._capture(plan, sp)
             plan.graph.launch(sp)
             return plan.out.clone()
+
+    @torch.no_grad()
+    def logits(self, features):
+        """[B, 2048] float32 features -> [B, 1008] float32 class logits, features @ fc.weight.T without fc.bias: every dot product
+        accumulated in float64 over k ascending and rounded to float32 once (one launch of frido_rows_dot, csrc/fidelity.hip)."""
+        from . import fidelity
+        fidelity._rows2d("FIDInceptionV3.logits", "features", features, self.fc.weight.shape[1])
+        if features.shape[0] == 0:
+            raise ValueError("FIDInceptionV3.logits: features must be a 2-D float32 tensor with at least one row")
+        _on_gpu(self._what, self, features)
+        return fidelity.rows_dot(features, self.fc.weight, mode=fidelity.STORE_F32)
 
 
 # ---- PatchGAN discriminator and the tokenizer's loss (taming/modules/discriminator/model.py, losses/vqperceptual.py) ------------------

@@ -268,3 +268,47 @@ def fid(stats_a, stats_b):
     weights ship with this repository, and with anything else in the extractor the number measures nothing about image quality."""
     from .fid import frechet_distance
     return frechet_distance(stats_a.mean(), stats_a.cov(), stats_b.mean(), stats_b.cov())
+
+
+@torch.no_grad()
+def fidelity_features(extractor, images, *, stats=None, feats=None, logits=None):
+    """ONE run of the Inception tower on `images` for whichever of the three metrics are being collected: `stats` (a
+    frido_amd.fid.FeatureStatistics, for fid) is updated with the features, `feats` (a frido_amd.fidelity.FeatureBank of width 2048, for
+    kid) gets them appended, `logits` (a FeatureBank of width 1008, for inception_score) gets extractor.logits(features) appended.
+    Returns (stats, feats, logits) as passed, None where None was.  extractor, images: as for fid_statistics.  Under torch.distributed
+    every rank collects its own shard; FeatureStatistics.all_gather_merge and FeatureBank.all_gather_concat join them in rank order."""
+    from .fid import FeatureStatistics
+    from .fidelity import FeatureBank
+    from .models import FIDInceptionV3
+    if not isinstance(extractor, FIDInceptionV3):
+        raise ValueError(f"fidelity_features: extractor must be a frido_amd.models.FIDInceptionV3, got {type(extractor).__name__}")
+    if stats is not None and not isinstance(stats, FeatureStatistics):
+        raise ValueError(f"fidelity_features: stats must be a frido_amd.fid.FeatureStatistics or None, got {type(stats).__name__}")
+    for name, bank in (("feats", feats), ("logits", logits)):
+        if bank is not None and not isinstance(bank, FeatureBank):
+            raise ValueError(f"fidelity_features: {name} must be a frido_amd.fidelity.FeatureBank or None, got {type(bank).__name__}")
+    f = extractor(images)
+    if stats is not None:
+        stats.update(f)
+    if feats is not None:
+        feats.append(f)
+    if logits is not None:
+        logits.append(extractor.logits(f))
+    return stats, feats, logits
+
+
+def inception_score(logit_bank, **kw):
+    """(mean, std) of the Inception Score of the logits fidelity_features collected (a FeatureBank or a float32 [N, C] tensor on the
+    GPU): frido_amd.fidelity.inception_score, whose docstring is the specification; splits=10, shuffle=True, rng_seed=2020.  No trained
+    weights ship with this repository, and with anything else in the extractor the number measures nothing about image quality."""
+    from .fidelity import inception_score as score
+    return score(logit_bank, **kw)
+
+
+def kid(bank_a, bank_b, **kw):
+    """(mean, std) of the Kernel Inception Distance between the features of two sides (FeatureBanks or float32 [n, D] tensors on the
+    GPU): frido_amd.fidelity.kernel_inception_distance, whose docstring is the specification; subsets=100, subset_size=1000, degree=3,
+    gamma=None, coef0=1.0, rng_seed=2020.  No trained weights ship with this repository, and with anything else in the extractor the
+    number measures nothing about image quality."""
+    from .fidelity import kernel_inception_distance
+    return kernel_inception_distance(bank_a, bank_b, **kw)

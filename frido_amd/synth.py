@@ -91,7 +91,7 @@ def _fill_inception(name, shape, rng, leaf):
     conv + BatchNorm + ReLU layers: conv weights INCEPTION_GAIN x He scale, sqrt(2 / fan_in), so that a layer hands on the second
     moment it received; per-channel DISTINCT BatchNorm statistics whose ratio gamma^2 / var averages about 1: running_var in
     [0.5, 1.5) (positive), weight in [0.75, 1.25), running_mean and bias 0.1 N(0, 1) -- about half of every output survives its ReLU
-    and no output dies or saturates on the way down (tests/test_fid_host.py asserts it).  fc, never run, gets fan-in scale."""
+    and no output dies or saturates on the way down (tests/test_fid_host.py asserts it).  fc (run by FIDInceptionV3.logits only) gets fan-in scale."""
     if leaf == "weight" and len(shape) == 4:
         return (rng.standard_normal(shape) * INCEPTION_GAIN * np.sqrt(2.0 / int(np.prod(shape[1:])))).astype(np.float32)
     if leaf == "weight" and len(shape) == 2:
