@@ -312,3 +312,13 @@ def kid(bank_a, bank_b, **kw):
     number measures nothing about image quality."""
     from .fidelity import kernel_inception_distance
     return kernel_inception_distance(bank_a, bank_b, **kw)
+
+
+def precision_recall(bank_real, bank_fake, k=3, **kw):
+    """{"precision", "recall", "density", "coverage", "f_score": floats, "counts": the integers behind them} between the features of the
+    real and the generated side (FeatureBanks or float32 [n, D] tensors on the GPU): frido_amd.manifold.prdc, whose docstring is the
+    specification; k=3, slab_bytes=512 MiB.  Under torch.distributed every rank gathers its banks with FeatureBank.all_gather_concat
+    first.  No trained weights ship with this repository, and with anything else in the extractor the numbers measure nothing about
+    image quality."""
+    from .manifold import prdc
+    return prdc(bank_real, bank_fake, k, **kw)

@@ -1,7 +1,7 @@
 """Fréchet Inception Distance between two sets of images, or between saved statistics.
 
     python tools/fid_npy.py A B [--ckpt inception.pth] [--batch 16] [--quant pil|np] [--save-a a.npz] [--save-b b.npz]
-                            [--isc] [--kid] [--save-feats-a fa.npz] [--save-feats-b fb.npz]
+                            [--isc] [--kid] [--prc] [--save-feats-a fa.npz] [--save-feats-b fb.npz]
 
 A and B are each either an .npy image stack -- uint8 [N, H, W, 3] (what `bench.py --dump-outputs DIR` writes) or float32 [N, 3, H, W] in
 [-1, 1] -- or an .npz of statistics (mu, sigma, n) written by --save-a / --save-b or FeatureStatistics.save: precomputed reference
@@ -12,6 +12,10 @@ Inception Distance between the sides (mean and std over --kid-subsets subsets of
 frido_amd.fidelity's, whose docstrings are their specification.  They need per-sample rows, which statistics files do not hold: for
 them A and B are image stacks or saved BANKS, an .npz with `features` [n, 2048] (--save-feats-a / --save-feats-b write them; a bank
 [n, 1008] is taken as logits and serves --isc alone).  A side given as a bank takes part in the distance line through its rows.
+
+--prc adds one line with improved precision and recall and density and coverage at the neighbourhood --prc-k
+(frido_amd.manifold.prdc, whose docstring is the specification).  Side B is the REAL one, as `fidelity --input1 PRED --input2 GT` has
+it; like --kid it wants features on both sides.
 
 --ckpt is a LOCAL state_dict of the published FID Inception weights (pt_inception-2015-12-05); nothing is downloaded.  WITHOUT it the
 extractor holds torch's initialisation and the printed number measures nothing about image quality; the tool says so."""
@@ -73,6 +77,8 @@ def main():
     ap.add_argument("--save-b", default=None)
     ap.add_argument("--isc", action="store_true", help="also print each side's Inception Score")
     ap.add_argument("--kid", action="store_true", help="also print the Kernel Inception Distance between the sides")
+    ap.add_argument("--prc", action="store_true", help="also print precision / recall and density / coverage of side A against the real side B")
+    ap.add_argument("--prc-k", type=int, default=3, help="the neighbourhood of --prc")
     ap.add_argument("--isc-splits", type=int, default=10)
     ap.add_argument("--kid-subsets", type=int, default=100)
     ap.add_argument("--kid-subset-size", type=int, default=1000)
@@ -95,7 +101,7 @@ def main():
     from frido_amd import pipeline
     sides = {}
     for side, path, save in (("a", args.a, args.save_feats_a), ("b", args.b, args.save_feats_b)):
-        sides[side] = statistics_of(path, extractor, args.batch, args.quant, want_feats=bool(args.kid or save), want_logits=args.isc)
+        sides[side] = statistics_of(path, extractor, args.batch, args.quant, want_feats=bool(args.kid or args.prc or save), want_logits=args.isc)
         if save:
             if sides[side][1] is None:
                 sys.exit(f"tools/fid_npy.py: {path} gives no features to save")
@@ -122,6 +128,13 @@ def main():
             sys.exit("tools/fid_npy.py: --kid needs features on both sides; a bank of logits holds none")
         mean, std = pipeline.kid(fa, fb, subsets=args.kid_subsets, subset_size=args.kid_subset_size)
         print(f"kernel_inception_distance {mean:.6f} +- {std:.6f}   n = {fa.n} / {fb.n}, subsets = {args.kid_subsets} x {args.kid_subset_size}{note}")
+    if args.prc:
+        fa, fb = sides["a"][1], sides["b"][1]
+        if fa is None or fb is None:
+            sys.exit("tools/fid_npy.py: --prc needs features on both sides; a bank of logits holds none")
+        r = pipeline.precision_recall(fb, fa, k=args.prc_k)
+        print(f"precision_recall precision {r['precision']:.6f} recall {r['recall']:.6f} f_score {r['f_score']:.6f} density {r['density']:.6f} "
+              f"coverage {r['coverage']:.6f}   n = {fa.n} / {fb.n}, k = {args.prc_k}{note}")
 
 
 if __name__ == "__main__":
